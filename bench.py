@@ -11,6 +11,13 @@ hash-sharded all-to-all of partial aggregates over RCCL and the owner-side merge
 final one-batch materialisation. Weak scaling: every rank owns 1B rows.
 
     python bench.py [--gpus N --steps K --warmup W]      (N > 1: launched by torch.distributed.run)
+
+A plain run does what the headline figure needs and nothing more: generate the columns, W warm-up
+steps and the clock warm-up, K timed steps, the result line. `--dump-outputs DIR` also writes the
+last timed step's result batch as .npy files. `--full` adds everything else the benchmark measures
+or checks, each in runs of its own outside the timed region: the stream-read ceilings (before any
+warm-up and after the timed steps), the result checks (COUNT(*) against an independent torch count,
+every group against the CPU port; for N > 1 the union of the owners' groups) and the CPU baselines.
 """
 from __future__ import annotations
 
@@ -200,9 +207,15 @@ def main():
     ap.add_argument("--steps", type=int, default=50)
     ap.add_argument("--warmup", type=int, default=10)
     ap.add_argument("--rows", type=lambda v: int(float(v)), default=1_000_000_000, help="rows per GPU (1e9 ok)")
-    ap.add_argument("--cpu-sample-rows", type=int, default=0, help="default: the same rows as one GPU")
+    ap.add_argument("--full", action="store_true",
+                    help="beside the headline figure: stream-read ceilings, result checks against torch and the "
+                         "CPU port, CPU baselines (each in runs of its own, outside the timed steps)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write the last step's result batch as DIR/<column>.npy (float64, "
+                         "rows in ascending key order; N > 1: each rank's groups as <column>_rank<r>.npy)")
+    ap.add_argument("--cpu-sample-rows", type=int, default=0, help="--full: default the same rows as one GPU")
     ap.add_argument("--cpu-threads", type=int, default=0)
-    ap.add_argument("--no-cpu", action="store_true")
+    ap.add_argument("--no-cpu", action="store_true", help="--full without the CPU baselines")
     ap.add_argument("--exchange", action="store_true",
                     help="run the multi-GPU exchange leg even with one rank (tests the N > 1 step on one GPU)")
     ap.add_argument("--exchange-impl", default="torch", choices=["torch", "native"],
@@ -215,13 +228,15 @@ def main():
                     help="N > 1: records per exchange slot (0: qe_hashagg_slot_capacity); a small value forces "
                          "the variable-size fallback")
     ap.add_argument("--verify-cpu", action="store_true",
-                    help="check every owner's groups against the CPU port over all ranks' rows (default for N > 1)")
-    ap.add_argument("--no-verify-cpu", action="store_true", help="N > 1: skip that check")
+                    help="N > 1: check every owner's groups against the CPU port over all ranks' rows (part of --full)")
+    ap.add_argument("--no-verify-cpu", action="store_true", help="N > 1: --full without that check")
     ap.add_argument("--dry-run", action="store_true",
                     help="print this rank's device plan (backend, device, device_id) as JSON and exit before any "
                          "GPU or process-group call (launcher-environment check)")
     ap.add_argument("--assume-gpus", type=int, default=-1, help="--dry-run only: visible GPU count to plan for")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # one process per GPU: this process only launches them (no torch, no GPU call here)
@@ -305,12 +320,17 @@ def main():
         if world > 1:
             dist.barrier()
 
-    # the same read ceiling before any warm-up (the device straight from idle), for the record
-    cc0 = (N.QeColumn * 3)(*[c.as_c() for c in cols])
-    ms0 = C.c_double()
-    shape0 = C.create_string_buffer(128)
-    N.check(N.lib().qe_stream_read_best(ctx.handle, cc0, 3, 1, C.byref(ms0), shape0, 128))
-    cold_gbs = rows * BYTES_PER_ROW / (ms0.value * 1e-3) / 1e9
+    def stream_read_gbs(reps):
+        """Best launch shape of a pure streaming read of the same 24 B/row (k, a, b), median of
+        `reps` each: (GB/s, the shape)."""
+        cc = (N.QeColumn * 3)(*[c.as_c() for c in cols])
+        ms = C.c_double()
+        shape = C.create_string_buffer(128)
+        N.check(N.lib().qe_stream_read_best(ctx.handle, cc, 3, reps, C.byref(ms), shape, 128))
+        return rows * BYTES_PER_ROW / (ms.value * 1e-3) / 1e9, shape.value.decode()
+
+    # --full: the read ceiling before any warm-up (the device straight from idle), for the record
+    cold_gbs = stream_read_gbs(1)[0] if args.full else None
     t_w = time.perf_counter()
     for _ in range(args.warmup):
         step()
@@ -352,31 +372,45 @@ def main():
     else:
         max_kernel_ms = avg_kernel_ms
 
-    # stream-read ceiling over the same 24 B/row (k, a, b): best launch shape, median of 5 each
-    cc = (N.QeColumn * 3)(*[c.as_c() for c in cols])
-    ms = C.c_double()
-    shape = C.create_string_buffer(128)
-    N.check(N.lib().qe_stream_read_best(ctx.handle, cc, 3, 5, C.byref(ms), shape, 128))
-    stream_gbs = rows * BYTES_PER_ROW / (ms.value * 1e-3) / 1e9
-
-    # Result checks before any number is printed: every group present once across owners, and
-    # COUNT(*) adds up to the rows an independent torch kernel counts as passing the predicate.
-    a_col = cols[1].values[:rows]
-    selected = int((a_col > (1 << 19)).sum().item())
-    groups = torch.tensor([keys[0].length, int(res[1].to_numpy().sum()), selected], dtype=torch.int64, device="cuda")
-    if world > 1:
-        if args.dist_backend == "gloo":
-            groups = groups.cpu()
-        dist.all_reduce(groups)
-    n_groups, count_total, selected_total = (int(x) for x in groups.tolist())
-    if n_groups != 1024 or count_total != selected_total:
-        sys.exit(f"bench: wrong result: {n_groups} groups (want 1024), COUNT(*) total {count_total} "
-                 f"(want {selected_total})")
+    # the last timed step's result batch, as its caller receives it (this rank's groups)
     kv = keys[0].to_numpy()
     rv = [r.to_numpy() for r in res]
-    my_groups = {int(kv[i]): tuple(int(r[i]) for r in rv) for i in range(keys[0].length)}
-    check = {"groups": n_groups, "count_star_total": count_total, "count_star_torch": selected_total}
-    if world > 1 and (args.verify_cpu or not args.no_verify_cpu):
+    if args.dump_outputs:
+        # rows in ascending key order (a GROUP BY result has none of its own: the table's slot
+        # order); float64 holds every value exactly (|SUM| < 2^53 up to 4e9 rows per group)
+        import numpy as np
+
+        out_dir = pathlib.Path(args.dump_outputs)
+        out_dir.mkdir(parents=True, exist_ok=True)
+        order = np.argsort(kv, kind="stable")
+        suffix = f"_rank{rank}" if world > 1 else ""
+        for name, v in zip(("k", "sum_a_plus_b", "count_star", "min_a", "max_b"), [kv] + rv):
+            np.save(out_dir / f"{name}{suffix}.npy", v[order].astype(np.float64))
+
+    # --full: stream-read ceiling after the timed steps (median of 5 per launch shape)
+    stream_gbs, stream_shape = stream_read_gbs(5) if args.full else (None, None)
+
+    check = {"groups": len(kv) if world == 1 else None}
+    my_groups = None
+    if args.full:
+        # Result checks before any number is printed: every group present once across owners, and
+        # COUNT(*) adds up to the rows an independent torch kernel counts as passing the predicate.
+        a_col = cols[1].values[:rows]
+        selected = int((a_col > (1 << 19)).sum().item())
+        groups = torch.tensor([len(kv), int(rv[1].sum()), selected], dtype=torch.int64, device="cuda")
+        if world > 1:
+            if args.dist_backend == "gloo":
+                groups = groups.cpu()
+            dist.all_reduce(groups)
+        n_groups, count_total, selected_total = (int(x) for x in groups.tolist())
+        if n_groups != 1024 or count_total != selected_total:
+            sys.exit(f"bench: wrong result: {n_groups} groups (want 1024), COUNT(*) total {count_total} "
+                     f"(want {selected_total})")
+        my_groups = {int(kv[i]): tuple(int(r[i]) for r in rv) for i in range(len(kv))}
+        check = {"groups": n_groups, "count_star_total": count_total, "count_star_torch": selected_total}
+    if world > 1 and (args.verify_cpu or (args.full and not args.no_verify_cpu)):
+        if my_groups is None:
+            my_groups = {int(kv[i]): tuple(int(r[i]) for r in rv) for i in range(len(kv))}
         # union of the owners' groups == the CPU port over every rank's rows (rows 0 .. world*rows)
         everyone = [None] * world
         dist.all_gather_object(everyone, my_groups)
@@ -411,6 +445,7 @@ def main():
         "world_size": world,
         "steps": args.steps,
         "warmup": args.warmup,
+        "full": args.full,
         "ms_per_step": ms_step,
         "kernel_ms": max_kernel_ms,
         "exchange_ms": avg_exch_ms,
@@ -445,7 +480,7 @@ def main():
             "stream_read_ceiling_gbs": stream_gbs,
             "stream_read_cold_gbs": cold_gbs,
             "prewarm_steps": prewarm_steps,
-            "stream_read_ceiling_shape": shape.value.decode(),
+            "stream_read_ceiling_shape": stream_shape,
         },
         "check": check,
     }
@@ -453,7 +488,7 @@ def main():
         line["comm"] = {"backend": args.dist_backend, "impl": args.exchange_impl,
                         "rccl_version": (".".join(str(x) for x in torch.cuda.nccl.version())
                                          if args.dist_backend == "nccl" else None)}
-    if rank == 0 and world == 1 and not args.no_cpu:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu:
         threads = args.cpu_threads or usable_cpus()
         sample = args.cpu_sample_rows or rows
         cpu_groups, line["cpu_baseline"] = cpu_baseline(sample, threads)

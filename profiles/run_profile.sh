@@ -4,7 +4,7 @@ set -o pipefail
 export TMPDIR=/tmp
 OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/prof
 mkdir -p $OUT
-B="python3 bench.py --steps ${STEPS:-3} --warmup 1 --no-cpu"
+B="python3 bench.py --steps ${STEPS:-3} --warmup 1 --full --no-cpu"
 timeout -k 10 300 rocprofv3 -L > $OUT/counters.txt 2>&1 || true
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/trace -o run -- $B > $OUT/trace.log 2>&1 || exit 1
 timeout -k 10 400 rocprofv3 --pmc FETCH_SIZE --output-format csv -d $OUT/fetch -o run -- $B > $OUT/fetch.log 2>&1 || exit 1

@@ -2,8 +2,8 @@
 launcher environment starts N ranks itself (torch.distributed.run as a child process), and each
 rank runs the exact timed step — stream-ordered fused C4 update with its global row base, the slot
 exchange of partial aggregates (or its variable-size fallback), the owner's merge, finalize. Rank 0
-then checks the union of every owner's groups against the CPU port over all ranks' rows (the
-default for N > 1; oracle/cpu_baseline.c restating Main.kt:615-651 and the K:1309-1325 merge).
+then checks the union of every owner's groups against the CPU port over all ranks' rows (with
+--full for N > 1; oracle/cpu_baseline.c restating Main.kt:615-651 and the K:1309-1325 merge).
 
 On the one-GPU box the ranks share cuda:0 over gloo (RCCL cannot put two ranks on one device); the
 RCCL leg itself is covered by tests/test_native_comm.py and the driver's multi-GPU runs."""
@@ -18,8 +18,8 @@ import pytest
 ROOT = pathlib.Path(__file__).resolve().parents[1]
 
 
-def _run(args, timeout=600):
-    env = dict(os.environ)
+def _run(args, timeout=600, **extra_env):
+    env = dict(os.environ, **extra_env)
     for k in ("WORLD_SIZE", "RANK", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     return subprocess.run([sys.executable, str(ROOT / "bench.py")] + args, capture_output=True, text=True,
@@ -72,7 +72,7 @@ def test_bench_two_ranks_self_launch(slot_records):
     """slot_records 0: the fixed-slot fast path; 40: every slot overflows (1024 groups / 2 owners),
     so all ranks take the counts + records fallback."""
     r = _run(["--gpus", "2", "--dist-backend", "gloo", "--rows", "1e7", "--steps", "2", "--warmup", "1",
-              "--slot-records", str(slot_records)])  # (the CPU check is the N > 1 default)
+              "--slot-records", str(slot_records), "--full"])  # (--full: the result checks, N > 1 the CPU check too)
     line = _line(r)
     assert line["n_gpus"] == 2 and line["world_size"] == 2
     assert line["value"] > 0 and line["exchange_ms"] is not None and line["exchange_ms"] > 0
@@ -80,3 +80,36 @@ def test_bench_two_ranks_self_launch(slot_records):
     assert line["check"]["count_star_total"] == line["check"]["count_star_torch"]
     assert line["check"]["cpu_port_groups_equal_all_ranks"] is True
     assert "gloo all-to-all" in line["config"]["parallelism"]
+
+
+@pytest.mark.gpu
+def test_bench_plain_run_dumps_its_outputs(tmp_path):
+    """A plain one-GPU run times exactly --steps steps and leaves out what --full adds; with
+    --dump-outputs it writes the last timed step's result batch (float64, ascending keys), which
+    equals the oracle's answer over the same seeded rows."""
+    import numpy as np
+
+    from oracle import gen
+    from oracle import semantics as S
+
+    n = 1_000_003
+    r = _run(["--gpus", "1", "--steps", "3", "--warmup", "1", "--rows", str(n), "--dump-outputs", str(tmp_path / "out")],
+             timeout=120, QE_BENCH_PREWARM_S="0")  # (no 2 s clock warm-up: the figure is not what is tested)
+    line = _line(r)
+    assert line["steps"] == 3 and line["warmup"] == 1 and line["full"] is False
+    assert line["ms_per_step"] > 0 and abs(line["value"] - n / (line["ms_per_step"] * 1e-3)) <= 1e-6 * line["value"]
+    assert line["unit"] == "rows/s" and line["higher_is_better"] is True and line["dtype"] == "int64"
+    assert "cpu_baseline" not in line and line["roofline"]["stream_read_ceiling_gbs"] is None
+    assert line["check"] == {"groups": 1024}
+    names = ("k", "sum_a_plus_b", "count_star", "min_a", "max_b")
+    assert sorted(p.name for p in (tmp_path / "out").iterdir()) == sorted(f"{c}.npy" for c in names)
+    got = [np.load(tmp_path / "out" / f"{c}.npy") for c in names]
+    assert all(g.dtype == np.float64 and g.shape == (1024,) for g in got)
+    k, _ = gen.generate(gen.GEN_MOD, 1024, 42, 0, 0, n)
+    a, _ = gen.generate(gen.GEN_MOD, 1 << 20, 42, 1, 0, n)
+    b, _ = gen.generate(gen.GEN_MOD, 1 << 20, 42, 2, 0, n)
+    ref = S.group_aggregate([k], [None], [a + b, None, a, b], [None] * 4,
+                            [S.AGG_SUM, S.AGG_COUNT_STAR, S.AGG_MIN, S.AGG_MAX], a > (1 << 19))
+    assert got[0].tolist() == sorted(float(key[0]) for key in ref)
+    for i in range(1024):
+        assert [float(v) for v in ref[(int(got[0][i]),)]] == [g[i] for g in got[1:]], i

@@ -8,7 +8,7 @@
 # or timed-out step). Steps:
 #   tests[:-k expr]    GPU test suite (pytest -m gpu), optionally a -k subset
 #   smoke              __graft_entry__.smoke()
-#   bench              bench.py default line (N=1)
+#   bench              bench.py --full line (N=1: headline, read ceilings, result checks, CPU baselines)
 #   configs            tools/bench_configs.py C2 C2L C2LN C3 C4 C5
 #   groups             tools/bench_groups.py GROUP BY cardinality sweep at 1B rows
 #   tripdata           tools/bench_tripdata.py (the reference's own query, K:1336)
@@ -45,7 +45,7 @@ for s in "$@"; do
     tests) step tests 1000 bash -c "python3 -u -m pytest tests -q -m gpu --timeout 280 --timeout-method thread > '$OUT/tests.txt' 2>&1" ;;
     tests:*) step tests 1000 bash -c "python3 -u -m pytest tests -q -m gpu --timeout 280 --timeout-method thread -k '${s#tests:}' > '$OUT/tests.txt' 2>&1" ;;
     smoke) step smoke 180 bash -c "python3 -c 'import __graft_entry__ as g; g.smoke()' > '$OUT/smoke.txt' 2>&1" ;;
-    bench) step bench 300 bash -c "python3 bench.py > '$OUT/bench.json' 2> '$OUT/bench.err'" ;;
+    bench) step bench 300 bash -c "python3 bench.py --full > '$OUT/bench.json' 2> '$OUT/bench.err'" ;;
     configs) step configs 600 bash -c "python3 tools/bench_configs.py C2 C2L C2LN C3 C4 C5 > '$OUT/configs${TAG:+_$TAG}.jsonl' 2> '$OUT/configs${TAG:+_$TAG}.err'" ;;
     groups) step groups 600 bash -c "python3 tools/bench_groups.py 1000000000 1024 4096 5800 8192 65536 1048576 > '$OUT/groups.jsonl' 2> '$OUT/groups.err'" ;;
     tripdata) step tripdata 300 bash -c "python3 tools/bench_tripdata.py > '$OUT/tripdata${TAG:+_$TAG}.json' 2> '$OUT/tripdata${TAG:+_$TAG}.err'" ;;

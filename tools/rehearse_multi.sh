@@ -8,6 +8,6 @@ OUT=${GRAFT_REPO_ROOT:-$PWD}/gpurun_out/multi
 mkdir -p $OUT
 for n in 2 4; do
   timeout -k 10 300 python3 -m torch.distributed.run --nnodes=1 --nproc-per-node $n --master-addr 127.0.0.1 \
-    --master-port $((29600 + n)) bench.py --gpus $n --steps 3 --warmup 1 --rows 100000000 --dist-backend gloo \
+    --master-port $((29600 + n)) bench.py --gpus $n --steps 3 --warmup 1 --rows 100000000 --dist-backend gloo --full \
     > $OUT/n$n.json 2> $OUT/n$n.err || exit 1
 done
