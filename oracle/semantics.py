@@ -18,6 +18,7 @@ unpinned by reference" and documented in include/qe_hip.h and DESIGN.md.
 from __future__ import annotations
 
 import math
+from fractions import Fraction
 from typing import Any, Dict, List, Optional, Sequence, Tuple
 
 import numpy as np
@@ -203,11 +204,21 @@ class AvgAccumulator(SumAccumulator):
 
 
 def _fsum(values) -> float:
-    vals = [float(v) for v in values]
-    if any(math.isnan(v) for v in vals):
-        return math.nan
-    pos = any(v == math.inf for v in vals)
-    neg = any(v == -math.inf for v in vals)
+    """The fp64 SUM contract: a NaN, or +Inf and -Inf together, give NaN; one sign of
+    infinity gives that infinity; finite inputs give the correctly rounded exact sum (ties to even),
+    +-Inf only when the exact sum itself overflows; an exact zero is +0.0."""
+    if isinstance(values, np.ndarray) and values.dtype == np.float64:
+        if np.isnan(values).any():
+            return math.nan
+        pos = bool((values == np.inf).any())
+        neg = bool((values == -np.inf).any())
+        vals = values.tolist()
+    else:
+        vals = [float(v) for v in values]
+        if any(math.isnan(v) for v in vals):
+            return math.nan
+        pos = any(v == math.inf for v in vals)
+        neg = any(v == -math.inf for v in vals)
     if pos and neg:
         return math.nan
     if pos:
@@ -215,9 +226,13 @@ def _fsum(values) -> float:
     if neg:
         return -math.inf
     try:
-        return math.fsum(vals)
-    except OverflowError:
-        return math.inf if sum(np.sign(vals)) > 0 else -math.inf
+        return math.fsum(vals) + 0.0  # (an exact zero: +0.0)
+    except OverflowError:  # an intermediate overflow of fsum's partials: the exact rational sum
+        q = sum((Fraction(v) for v in vals), Fraction(0))
+        try:
+            return float(q)  # correctly rounded, ties to even
+        except OverflowError:
+            return math.inf if q > 0 else -math.inf
 
 
 def make_accumulator(fn: int, is_f64: bool):
@@ -286,12 +301,14 @@ def global_aggregate(values: np.ndarray, valid=None, mask=None, mask_valid=None)
         out.update(sum=None, min=None, max=None, avg=None)
         return out
     if values.dtype == np.float64:
-        s = _fsum(x.tolist()) if len(x) < 2_000_000 else float(np.sum(x.astype(np.longdouble)))
+        s = _fsum(x)
         out.update(sum=s, min=_minmax_f64(x, False), max=_minmax_f64(x, True), avg=s / len(x))
     else:
         s = int(np.sum(x.astype(np.uint64), dtype=np.uint64).view(np.int64)) if len(x) else 0
-        out.update(sum=s, min=int(x.min()), max=int(x.max()),
-                   avg=float(np.sum(x.astype(np.longdouble)) / len(x)))
+        # AVG of an integer column: each value converted to fp64 (round to nearest even), those
+        # summed exactly, one division. (qe_agg_global's int64 AVG is a compensated sum of the
+        # converted values, not certified: the one global result outside the exact contract.)
+        out.update(sum=s, min=int(x.min()), max=int(x.max()), avg=_fsum(x.astype(np.float64)) / len(x))
     return out
 
 
@@ -350,11 +367,12 @@ def group_aggregate(keys: Sequence[np.ndarray], key_valid: Sequence[Optional[np.
                 vals.append(None)
             elif fn == AGG_SUM:
                 if y.dtype == np.float64:
-                    vals.append(float(np.sum(y.astype(np.longdouble))) if len(y) > 4096 else _fsum(y.tolist()))
+                    vals.append(_fsum(y))
                 else:
                     vals.append(int(np.sum(y.astype(np.uint64), dtype=np.uint64).view(np.int64)))
             elif fn == AGG_AVG:
-                vals.append(float(np.sum(y.astype(np.longdouble)) / len(y)))
+                # integer inputs: float(int) per value (round to nearest even), as AvgAccumulator
+                vals.append(_fsum(y.astype(np.float64)) / len(y))
             elif y.dtype == np.float64:
                 vals.append(_minmax_f64(y, fn == AGG_MAX))
             else:

@@ -174,7 +174,7 @@ def main():
 
         same = all(e == everyone[0] for e in everyone)  # every rank merged to the same bits
         ok = (same and r.rows == want["rows"] and r.count == want["count"]
-              and S.rows_equal(f64_from_bits(r.sum), want["sum"], 1e-9)
+              and S.rows_equal(f64_from_bits(r.sum), want["sum"], 0.0)
               and S.rows_equal(f64_from_bits(r.min), want["min"]) and S.rows_equal(f64_from_bits(r.max), want["max"]))
         results["global"] = {"ok": bool(ok)}
     if rank == 0:

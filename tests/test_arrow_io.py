@@ -138,5 +138,4 @@ def test_prefetch_import_pipeline(gpu_ctx):
     for key, want in ref.items():
         g = got[key]
         for j, (a, b) in enumerate(zip(g, want)):
-            rel = 1e-9 if fns[j] == N.AGG_SUM else 0.0
-            assert S.rows_equal(None if a is None else (float(a) if fns[j] != N.AGG_COUNT else int(a)), b, rel), (key, j)
+            assert S.rows_equal(None if a is None else (float(a) if fns[j] != N.AGG_COUNT else int(a)), b, 0.0), (key, j)

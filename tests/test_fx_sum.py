@@ -18,6 +18,9 @@ from fractions import Fraction
 import numpy as np
 import pytest
 
+import aggdata
+from oracle.semantics import _fsum as fsum  # the contract: exact where math.fsum's partials overflow
+
 NATIVE = pathlib.Path(__file__).resolve().parent / "native"
 LIB = NATIVE / "_build" / "libqe_fx_host.so"
 
@@ -150,15 +153,6 @@ def test_tiny_inputs(fx):
     assert fx([3.7e-5, -3.7e-5])[0] == 0.0
 
 
-def fsum(xs):
-    """math.fsum, which raises on an intermediate overflow (1e308 + 1e308 - 1e308): the exact sum
-    then (its documented value without the overflow)."""
-    try:
-        return math.fsum(xs)
-    except OverflowError:
-        return exact(xs)
-
-
 def test_full_range_matches_fsum(fx):
     """The verdict's full-range cases, bit for bit with math.fsum: groups of 1e-40 values, 1e300 with
     unit terms, subnormals, and an intermediate overflow that cancels."""
@@ -191,6 +185,21 @@ def test_overflow_and_underflow_edges(fx):
     for xs in ([tiny, -5e-324], [5e-324] * 3, [tiny / 2, tiny / 2], [-5e-324], [tiny * 3, -tiny * 2.5]):
         v, _, _ = fx(xs, 2)
         assert same(v, exact(xs)) and same(v, fsum(xs)), xs
+
+
+@pytest.mark.parametrize("name,xs", aggdata.BOUNDARY_CASES, ids=[c[0] for c in aggdata.BOUNDARY_CASES])
+def test_rounding_boundaries(fx, name, xs):
+    """The rounding-boundary groups of tests/test_fp64_sum_gpu.py on the host build: a device
+    failure there is in the arithmetic header if the case fails here, outside it otherwise. Rows in
+    one slot and spread over slots, through the plain accumulator and the LDS-window split."""
+    want = fsum(xs)
+    assert same(want, exact(xs))
+    rng = np.random.default_rng(len(name))
+    for ns in (1, 2, 5):
+        v, err, _ = fx(rng.permutation(np.array(xs)), ns, rng.permutation(ns))
+        assert not err and same(v, want), (name, ns, v, want)
+        v, err, _, _ = window(fx, rng.permutation(np.array(xs)), ns)
+        assert not err and same(v, want), (name, "window", ns, v, want)
 
 
 def test_chunk_merges_equal_rows(fx):

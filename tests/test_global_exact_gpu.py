@@ -14,6 +14,9 @@ import math
 import numpy as np
 import pytest
 
+import global_merge
+from oracle.semantics import _fsum
+
 pytestmark = pytest.mark.gpu
 
 
@@ -75,20 +78,6 @@ def test_well_conditioned_is_fsum(gpu_ctx):
         assert _bits(f64_from_bits(r.sum)) == _bits(want)
 
 
-def _fsum(xs):
-    """math.fsum; on its intermediate-overflow error the exact sum (fractions, ties to even)."""
-    from fractions import Fraction
-
-    try:
-        return math.fsum(xs)
-    except OverflowError:
-        q = sum((Fraction(float(v)) for v in xs), Fraction(0))
-        try:
-            return float(q)
-        except OverflowError:
-            return math.inf if q > 0 else -math.inf
-
-
 FULL_RANGE = [[1e-40] * 5000, [1e300] + [1.0] * 3000 + [-1e300], [5e-324] * 4097, [1e308, 1e308, -1e308],
               [1e308, 1e308], [-1e-320, 3e-322, 2.2250738585072014e-308, -5e-324], [2.0 ** 200, 1.0, -(2.0 ** 200)]]
 
@@ -121,36 +110,10 @@ def test_specials(gpu_ctx, vals, want):
 
 def _merge(gpu_ctx, pieces):
     """qe_agg_global_partial per piece, qe_agg_global_merge, and the exact round when it asks."""
-    import torch
-
     from kquery import native as N
-    from kquery.columnar import DeviceColumn
 
-    parts, words, cols = [], [], []
-    base = 0
-    for x in pieces:
-        p = torch.empty(N.GLOBAL_PARTIAL_BYTES, dtype=torch.uint8, device=gpu_ctx.torch_device)
-        c = DeviceColumn.from_numpy(N.TYPE_FLOAT64, x, None, ctx=gpu_ctx)
-        cols.append(c)
-        cc = c.as_c()
-        N.check(N.lib().qe_agg_global_partial(gpu_ctx.handle, N.C.byref(cc), None, base, N.C.c_void_p(p.data_ptr())))
-        parts.append(p)
-        base += len(x)
-    buf = torch.cat(parts)
-    out = N.QeGlobalAgg()
-    st = N.lib().qe_agg_global_merge(gpu_ctx.handle, N.TYPE_FLOAT64, N.C.c_void_p(buf.data_ptr()), len(pieces),
-                                     N.C.byref(out))
-    if st == N.QE_NEED_EXACT:
-        for c in cols:
-            w = torch.empty(N.GLOBAL_EXACT_BYTES, dtype=torch.uint8, device=gpu_ctx.torch_device)
-            cc = c.as_c()
-            N.check(N.lib().qe_agg_global_exact_partial(gpu_ctx.handle, N.C.byref(cc), None, N.C.c_void_p(w.data_ptr())))
-            words.append(w)
-        allw = torch.cat(words)
-        st = N.lib().qe_agg_global_merge_exact(gpu_ctx.handle, N.C.c_void_p(allw.data_ptr()), len(pieces),
-                                               N.C.byref(out))
-    N.check(st)
-    return out, bool(words)
+    parts, cols = global_merge.partials(gpu_ctx, [(x, None) for x in pieces], N.TYPE_FLOAT64)
+    return global_merge.merge(gpu_ctx, parts, cols, N.TYPE_FLOAT64)
 
 
 def test_merge_of_cancelling_shards_is_exact(gpu_ctx):

@@ -4,6 +4,7 @@ import ctypes as C
 import json
 import math
 import pathlib
+from fractions import Fraction
 
 import numpy as np
 import pytest
@@ -125,21 +126,27 @@ def test_three_valued_logic_golden():
 
 
 # ---- vectorised group-by == literal HashAggregateExec loop (K:615-651) -------------------------------
-@pytest.mark.parametrize("seed", [1, 2, 3])
+@pytest.mark.parametrize("seed", [1, 2, 3, 4, 5])
 def test_group_aggregate_matches_literal_loop(seed):
+    """Bit for bit, fp64 SUM / AVG included: both forms state the exact contract (_fsum). Seed 4
+    has groups above 4096 values, seed 5 int64 AVG inputs near 2^62 (float(int) rounds each value,
+    the converted values are summed exactly, one division)."""
     rng = np.random.default_rng(seed)
-    n = 3000
+    n = 40_000 if seed == 4 else 3000
     k = rng.integers(-3, 4, n).astype(np.int64)
     kv = rng.random(n) > 0.1
     x = rng.normal(size=n)
-    x[rng.random(n) < 0.05] = np.nan
+    x[rng.random(n) < (0.0005 if seed == 4 else 0.05)] = np.nan
     x[rng.random(n) < 0.05] = 0.0
     x[rng.random(n) < 0.05] = -0.0
     xv = rng.random(n) > 0.2
-    y = rng.integers(-2**62, 2**62, n).astype(np.int64)
-    fns = [S.AGG_MAX, S.AGG_MIN, S.AGG_SUM, S.AGG_COUNT, S.AGG_COUNT_STAR, S.AGG_MAX, S.AGG_SUM, S.AGG_AVG]
-    ins = [x, x, x, x, None, y, y, y]
-    insv = [xv, xv, xv, xv, None, None, None, None]
+    if seed == 5:
+        y = (rng.choice([-1, 1], n) * (2**62 - rng.integers(1, 2**12, n))).astype(np.int64)
+    else:
+        y = rng.integers(-2**62, 2**62, n).astype(np.int64)
+    fns = [S.AGG_MAX, S.AGG_MIN, S.AGG_SUM, S.AGG_COUNT, S.AGG_COUNT_STAR, S.AGG_MAX, S.AGG_SUM, S.AGG_AVG, S.AGG_AVG]
+    ins = [x, x, x, x, None, y, y, y, x]
+    insv = [xv, xv, xv, xv, None, None, None, None, xv]
     vec = S.group_aggregate([k], [kv], ins, insv, fns)
     keys = [[int(a) if ok else None for a, ok in zip(k, kv)]]
     rows_in = []
@@ -150,12 +157,15 @@ def test_group_aggregate_matches_literal_loop(seed):
             rows_in.append([float(a) if (v is None or ok) else None for a, ok in zip(arr, v if v is not None else [True] * n)])
         else:
             rows_in.append([int(a) for a in arr])
-    lit = S.hash_aggregate_rows(keys, rows_in, fns, [True, True, True, True, False, False, False, False])
+    lit = S.hash_aggregate_rows(keys, rows_in, fns, [True, True, True, True, False, False, False, False, True])
     assert set(vec) == set(lit)
+    finite = 0
     for key in lit:
         for j, (a, b) in enumerate(zip(vec[key], lit[key])):
-            rel = 1e-12 if fns[j] in (S.AGG_SUM, S.AGG_AVG) and isinstance(b, float) else 0.0
-            assert S.rows_equal(a, b, rel), (key, j, a, b)
+            assert S.rows_equal(a, b, 0.0), (key, j, a, b)
+        finite += math.isfinite(lit[key][2])
+    if seed == 4:
+        assert max(v[3] for v in lit.values()) > 4096 and finite >= 1
 
 
 def test_global_aggregate_int_wrap_and_empty():
@@ -169,7 +179,64 @@ def test_global_aggregate_int_wrap_and_empty():
 def test_fsum_special_values():
     assert math.isnan(S._fsum([1.0, math.nan]))
     assert S._fsum([math.inf, 1.0]) == math.inf
+    assert S._fsum([-math.inf, 1e308, 1e308]) == -math.inf
     assert math.isnan(S._fsum([math.inf, -math.inf]))
+    assert math.isnan(S._fsum(np.array([1.0, math.inf, -math.inf])))
+    assert math.isnan(S._fsum(np.array([math.inf, math.nan])))
+
+
+def test_fsum_is_the_exact_sum_where_fsum_overflows():
+    """An intermediate overflow of math.fsum is not an overflow of the sum: +-Inf only
+    when the correctly rounded exact sum is out of range."""
+    mx = np.finfo(np.float64).max
+    assert S._fsum([1e308, 1e308, -1e308]) == 1e308
+    assert S._fsum([1e308, 1e308, -1.0, -1.0, -1.0]) == math.inf
+    assert S._fsum([-1e308, -1e308, 1.0, 1.0, 1.0]) == -math.inf
+    assert S._fsum([mx, 2.0 ** 970]) == math.inf  # half way to 2^1024: ties to even, up
+    assert S._fsum([mx, 2.0 ** 969]) == mx
+    assert S._fsum([-mx, -(2.0 ** 970)]) == -math.inf and S._fsum([-mx, -(2.0 ** 969)]) == -mx
+    assert S._fsum(np.array([mx, mx, -mx])) == mx
+    for zero in ([-0.0, -0.0], [-0.0], [3.7e-5, -3.7e-5, -0.0], np.array([-0.0, -0.0])):
+        assert math.copysign(1.0, S._fsum(zero)) == 1.0 and S._fsum(zero) == 0.0
+
+
+def test_avg_of_a_large_cancelling_group_is_exact():
+    """10^5 cancelling values: SUM is float(exact rational sum), AVG that / n in one division — in
+    the vectorised oracle (any group size), the global one and the literal accumulator."""
+    rng = np.random.default_rng(8)
+    n = 100_000
+    x = rng.normal(size=n) * np.exp2(rng.integers(-40, 60, n).astype(np.float64))
+    x[: n // 2] = -x[n // 2:][::-1]  # cancels exactly ...
+    x[7] += 2.0 ** -30  # ... but for this
+    x[n - 9] = 1e-30
+    x = x[rng.permutation(n)]
+    q = sum((Fraction(float(v)) for v in x), Fraction(0))
+    want = float(q)
+    assert want != 0.0 and want != float(np.sum(x))  # (plain summation loses it)
+    got = S.group_aggregate([np.zeros(n, dtype=np.int64)], [None], [x, x], [None, None], [S.AGG_SUM, S.AGG_AVG])
+    assert got[(0,)] == [want, want / n]
+    g = S.global_aggregate(x)
+    assert g["sum"] == want and g["avg"] == want / n
+    acc = S.AvgAccumulator()
+    for v in x.tolist():
+        acc.accumulate(v)
+    assert acc.finalValue() == want / n
+
+
+def test_int_avg_converts_each_value_then_sums_exactly():
+    """AVG of int64 inputs near 2^62: float(int) per value (round to nearest even), the exact sum of
+    those, one division — not the exact integer sum, and not a long double one."""
+    y = np.array([2**62 - 1, 2**62 - 1, -(2**62) + 257, 3], dtype=np.int64)
+    want = math.fsum([float(int(v)) for v in y]) / 4
+    assert want != float(Fraction(int(y.astype(object).sum()), 4))
+    got = S.group_aggregate([np.zeros(4, dtype=np.int64)], [None], [y], [None], [S.AGG_AVG])
+    assert got[(0,)] == [want]
+    assert S.global_aggregate(y)["avg"] == want
+
+
+def test_no_extended_precision_in_the_oracle():
+    src = pathlib.Path(S.__file__).read_text()
+    assert "long" + "double" not in src
 
 
 # ---- C restatement (CPU baseline) == numpy oracle -------------------------------------------------------
