@@ -584,6 +584,13 @@ int qe_hashagg_last_kernel_signature(qe_hashagg* agg, uint64_t* sig);
 /* Whether the last update ran a plan-specialised kernel (1) or the generic one (0), and why
  * not (NUL-terminated note, may be NULL). */
 int qe_hashagg_last_kernel_kind(qe_hashagg* agg, int32_t* specialized, char* note, int32_t note_len);
+/* Measurement hook: what the last update call wrote into record chunks (the spilling pass and the
+ * chunked radix scatter write their intermediate records into 2048-record chunks that open streams
+ * claim from a device counter): chunks claimed, how many of them hold exactly 2048 records (a
+ * stream filled them and went on to the next), and the records in all of them. All zeros when the
+ * update wrote no chunked records, or wrote 32-bit records that a value did not fit and re-read
+ * its rows instead. Synchronises the ctx stream. */
+int qe_hashagg_last_chunk_stats(qe_hashagg* agg, int64_t* chunks, int64_t* full_chunks, int64_t* records);
 
 /* ---- UTF-8 group keys (K:620-627: row key = String(bytes), HashMap content equality) ------
  * A device string dictionary maps each distinct byte string to a dense int32 code, stable for

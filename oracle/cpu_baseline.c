@@ -297,6 +297,7 @@ typedef struct {
   int64_t *k, *a, *b;
   int64_t row0, n, nkeys;
   uint64_t seed;
+  uint64_t amod, bmod; /* a = u1 % amod, b = u2 % bmod */
 } gen_job;
 
 static void* gen_main(void* arg) { /* untimed: regenerate the synthetic rows (oracle/gen.py) */
@@ -304,8 +305,8 @@ static void* gen_main(void* arg) { /* untimed: regenerate the synthetic rows (or
   for (int64_t i = 0; i < g->n; ++i) {
     const uint64_t r = (uint64_t)(g->row0 + i);
     g->k[i] = (int64_t)(gen_u64(g->seed, 0, r) % (uint64_t)g->nkeys);
-    g->a[i] = (int64_t)(gen_u64(g->seed, 1, r) % (1ull << 20));
-    g->b[i] = (int64_t)(gen_u64(g->seed, 2, r) % (1ull << 20));
+    g->a[i] = (int64_t)(gen_u64(g->seed, 1, r) % g->amod);
+    g->b[i] = (int64_t)(gen_u64(g->seed, 2, r) % g->bmod);
   }
   return NULL;
 }
@@ -322,9 +323,10 @@ static double now_s(void) {
 }
 
 /* Returns seconds spent in the (timed) query; fills out[] (cap entries) and *ngroups.
- * Data: k = u0 % 1024, a = u1 % 2^20, b = u2 % 2^20 for rows row0..row0+rows-1. */
-double qe_cpu_c4(int64_t row0, int64_t rows, uint64_t seed, int threads, int64_t threshold, int64_t nkeys,
-                 qe_group_out* out, int64_t cap, int64_t* ngroups) {
+ * Data: k = u0 % nkeys, a = u1 % amod, b = u2 % bmod for rows row0..row0+rows-1 (amod, bmod > 0:
+ * the value ranges are the caller's, e.g. values past 32 bits). */
+double qe_cpu_c4_mod(int64_t row0, int64_t rows, uint64_t seed, int threads, int64_t threshold, int64_t nkeys,
+                     int64_t amod, int64_t bmod, qe_group_out* out, int64_t cap, int64_t* ngroups) {
   if (threads < 1) threads = 1;
   int64_t* k = (int64_t*)malloc(rows * sizeof(int64_t));
   int64_t* a = (int64_t*)malloc(rows * sizeof(int64_t));
@@ -335,7 +337,7 @@ double qe_cpu_c4(int64_t row0, int64_t rows, uint64_t seed, int threads, int64_t
   gen_job* jobs = (gen_job*)calloc(threads, sizeof(gen_job));
   for (int t = 0; t < threads; ++t) {
     const int64_t s = t * per, e = (s + per < rows) ? s + per : rows;
-    jobs[t] = (gen_job){k + s, a + s, b + s, row0 + s, e > s ? e - s : 0, nkeys, seed};
+    jobs[t] = (gen_job){k + s, a + s, b + s, row0 + s, e > s ? e - s : 0, nkeys, seed, (uint64_t)amod, (uint64_t)bmod};
     pthread_create(&tid[t], NULL, gen_main, &jobs[t]);
   }
   for (int t = 0; t < threads; ++t) pthread_join(tid[t], NULL);
@@ -390,6 +392,12 @@ double qe_cpu_c4(int64_t row0, int64_t rows, uint64_t seed, int threads, int64_t
   free(a);
   free(b);
   return t1 - t0;
+}
+
+/* The BASELINE configuration's data: a = u1 % 2^20, b = u2 % 2^20. */
+double qe_cpu_c4(int64_t row0, int64_t rows, uint64_t seed, int threads, int64_t threshold, int64_t nkeys,
+                 qe_group_out* out, int64_t cap, int64_t* ngroups) {
+  return qe_cpu_c4_mod(row0, rows, seed, threads, threshold, nkeys, 1ll << 20, 1ll << 20, out, cap, ngroups);
 }
 
 /* ---- a tuned CPU implementation of the same query, reported beside the port ("plus
@@ -457,7 +465,7 @@ double qe_cpu_c4_fast(int64_t row0, int64_t rows, uint64_t seed, int threads, in
   gen_job* jobs = (gen_job*)calloc(threads, sizeof(gen_job));
   for (int t = 0; t < threads; ++t) {
     const int64_t s = t * per, e = (s + per < rows) ? s + per : rows;
-    jobs[t] = (gen_job){k + s, a + s, b + s, row0 + s, e > s ? e - s : 0, nkeys, seed};
+    jobs[t] = (gen_job){k + s, a + s, b + s, row0 + s, e > s ? e - s : 0, nkeys, seed, 1ull << 20, 1ull << 20};
     pthread_create(&tid[t], NULL, gen_main, &jobs[t]);
   }
   for (int t = 0; t < threads; ++t) pthread_join(tid[t], NULL);

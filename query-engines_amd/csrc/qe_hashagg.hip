@@ -1484,6 +1484,7 @@ struct qe_hashagg {
   // radix-partitioned updates (expected groups beyond the LDS table): counts / offsets, records
   int64_t* part_cnt = nullptr;
   size_t part_cnt_bytes = 0;
+  int64_t chunk_cap = 0;  // chunk ids of the table the last update left in part_cnt (0: it wrote no chunked records)
   uint8_t* part_rec = nullptr;
   size_t part_rec_bytes = 0;
   int64_t* part_slc = nullptr;  // slice descriptors of the partition-aggregate pass
@@ -2152,6 +2153,7 @@ static int partition_rows(qe_hashagg* h, Plan& P, hipFunction_t* fn, int* grid) 
     P.part_tw = tw;
     P.part_rec = h->part_rec;
     P.part_chunk = meta;
+    h->chunk_cap = cmax;
     QE_TRY(jit_launch(ctx, fs, (int)g, P, sblock));
     QE_TRY(launch_check("qe_pscatter"));
     const unsigned pg = (unsigned)div_up((uint64_t)cmax, CHUNK_PER_WG);
@@ -2496,6 +2498,7 @@ static int spill_update(qe_hashagg* h, Plan& P, size_t lds, int64_t rows, bool* 
   QE_TRY(grow_buffer(&h->part_slc, &h->part_slc_bytes, (size_t)(2 + 2 * (tmax + SB)) * 8, ctx, "spill slices"));
   QE_TRY(ensure_defer(h, cmax * PART_CH));  // the aggregation pass's retry bitmaps index record slots
   *used = true;
+  h->chunk_cap = cmax;
   QE_HIP(hipMemsetAsync(meta, 0, 8, ctx->stream));
   if (L.narrow) QE_HIP(hipMemsetAsync(h->ctl + 7, 0, 8, ctx->stream));
   // kept share: as many groups as one LDS table holds at a 6/8 load, the rest spilled (4096
@@ -2527,6 +2530,7 @@ static int spill_update(qe_hashagg* h, Plan& P, size_t lds, int64_t rows, bool* 
     // the columns instead (mp_pass -1), and this state's records are 64-bit from now on.
     h->narrow_failed = false;
     h->part_wide = true;
+    h->chunk_cap = 0;  // (the records written are not the update's)
     Plan R = P;
     R.part_narrow = 0;
     R.mp_pass = -1;
@@ -2592,6 +2596,7 @@ static int run_update(qe_hashagg* h, Plan& P) {
   h->known_groups = -1;
   h->last_kernel_ms = 0.0;
   h->last_launches = 0;
+  h->chunk_cap = 0;
   // groups beyond the LDS table: radix-partition the selected rows by key hash first, then
   // aggregate record slices in LDS (events bracket the whole sequence)
   hipFunction_t pfn = nullptr;
@@ -2859,6 +2864,7 @@ static int run_update(qe_hashagg* h, Plan& P) {
     // this state's partitioned updates use 64-bit words from now on
     h->narrow_failed = false;
     h->part_wide = true;
+    h->chunk_cap = 0;
     P = P_rows;
     pfn = nullptr;
     // the repeat is timed from here: the attempt just settled is already in last_kernel_ms once
@@ -3058,6 +3064,29 @@ int qe_hashagg_last_kernel_time(qe_hashagg* h, double* ms, int32_t* launches) {
   QE_TRY(settle_pending(h));
   *ms = h->last_kernel_ms;
   if (launches) *launches = h->last_launches;
+  return QE_OK;
+}
+
+int qe_hashagg_last_chunk_stats(qe_hashagg* h, int64_t* chunks, int64_t* full_chunks, int64_t* records) {
+  QE_CHECK(h && chunks && full_chunks && records, QE_ERR_INVALID_ARG, "null argument");
+  QE_TRY(ctx_enter(h->ctx));
+  QE_TRY(settle_pending(h));
+  *chunks = *full_chunks = *records = 0;
+  if (h->chunk_cap <= 0 || !h->part_cnt) return QE_OK;
+  QE_TRY(ctx_sync(h->ctx));
+  // part_cnt: [0] chunk ids handed out | per id (bucket << 32 | records), < 0: an id nothing took
+  int64_t ids = 0;
+  QE_HIP(hipMemcpy(&ids, h->part_cnt, 8, hipMemcpyDeviceToHost));
+  ids = std::max<int64_t>(0, std::min<int64_t>(ids, h->chunk_cap));
+  std::vector<int64_t> meta((size_t)ids);
+  if (ids) QE_HIP(hipMemcpy(meta.data(), h->part_cnt + 1, (size_t)ids * 8, hipMemcpyDeviceToHost));
+  for (const int64_t w : meta) {
+    if (w < 0) continue;
+    const int64_t fill = w & 0xFFFFFFFFll;
+    *chunks += 1;
+    *full_chunks += fill == PART_CH ? 1 : 0;
+    *records += fill;
+  }
   return QE_OK;
 }
 

@@ -218,6 +218,12 @@ class HashAggregateState:
         N.check(N.lib().qe_hashagg_last_kernel_kind(self.handle, N.C.byref(k), buf, 512))
         return bool(k.value), buf.value.decode(errors="replace")
 
+    def last_chunk_stats(self):
+        """(chunks, full_chunks, records) the last update wrote as chunked records; zeros if none."""
+        c, f, r = N.C.c_int64(), N.C.c_int64(), N.C.c_int64()
+        N.check(N.lib().qe_hashagg_last_chunk_stats(self.handle, N.C.byref(c), N.C.byref(f), N.C.byref(r)))
+        return c.value, f.value, r.value
+
     def reset(self) -> None:
         N.check(N.lib().qe_hashagg_reset(self.handle))
         # _held stays: the discarded update's kernel may still be reading those columns on the

@@ -262,6 +262,7 @@ SIGNATURES = [
     ("qe_hashagg_last_kernel_time", C.c_int, [_P, C.POINTER(C.c_double), C.POINTER(C.c_int32)]),
     ("qe_hashagg_last_kernel_signature", C.c_int, [_P, C.POINTER(C.c_uint64)]),
     ("qe_hashagg_last_kernel_kind", C.c_int, [_P, C.POINTER(C.c_int32), C.c_char_p, C.c_int32]),
+    ("qe_hashagg_last_chunk_stats", C.c_int, [_P, C.POINTER(C.c_int64), C.POINTER(C.c_int64), C.POINTER(C.c_int64)]),
     ("qe_strdict_create", C.c_int, [_P, C.c_int64, _PP]),
     ("qe_strdict_destroy", C.c_int, [_P]),
     ("qe_strdict_size", C.c_int, [_P, _I64P]),

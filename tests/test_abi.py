@@ -29,6 +29,19 @@ def test_library_exports_every_declared_symbol():
     assert set(names) == bound, set(names) ^ bound
 
 
+def test_measurement_hooks_are_declared_and_bound():
+    """The hooks tests and tools read what an update did through (include/qe_hip.h "Measurement hook")."""
+    from kquery import native as N
+
+    lib = N.load_library()
+    sigs = {s[0]: s for s in N.SIGNATURES}
+    for name in ("qe_hashagg_last_kernel_time", "qe_hashagg_last_kernel_signature", "qe_hashagg_last_kernel_kind",
+                 "qe_hashagg_last_chunk_stats"):
+        assert name in _declared_functions() and hasattr(lib, name)
+    _, res, args = sigs["qe_hashagg_last_chunk_stats"]
+    assert res is C.c_int and args[1:] == [C.POINTER(C.c_int64)] * 3
+
+
 def test_abi_version_and_error_string():
     from kquery import native as N
 

@@ -256,6 +256,9 @@ def _oracle_lib():
                               C.POINTER(_G), C.c_int64, C.POINTER(C.c_int64)]
     lib.qe_cpu_c4_fast.restype = C.c_double
     lib.qe_cpu_c4_fast.argtypes = lib.qe_cpu_c4.argtypes
+    lib.qe_cpu_c4_mod.restype = C.c_double
+    lib.qe_cpu_c4_mod.argtypes = [C.c_int64, C.c_int64, C.c_uint64, C.c_int, C.c_int64, C.c_int64, C.c_int64, C.c_int64,
+                                  C.POINTER(_G), C.c_int64, C.POINTER(C.c_int64)]
     return lib
 
 
@@ -277,6 +280,30 @@ def test_cpu_baseline_matches_oracle(threads, row0, fast):
                             [S.AGG_SUM, S.AGG_COUNT_STAR, S.AGG_MIN, S.AGG_MAX], a > (1 << 19))
     got = {(o.key,): [o.sum, o.count, o.min, o.max] for o in out[: ng.value]}
     assert got == ref
+
+
+@pytest.mark.parametrize("bits,thr_bits", [(20, 16), (40, 36)])
+def test_cpu_baseline_chosen_value_ranges(bits, thr_bits):
+    """qe_cpu_c4_mod (a = u1 % amod, b = u2 % bmod; tests/test_chunk_turnover.py's reference): group
+    for group the numpy oracle over the generator's columns, past the 4096 groups the tuned leg
+    holds and with values past 32 bits; at the BASELINE moduli it is qe_cpu_c4."""
+    lib = _oracle_lib()
+    n, row0, nkeys, mod, thr = 200_003, 5, 6500, 1 << bits, 1 << thr_bits
+    out = (_G * 8192)()
+    ng = C.c_int64()
+    assert lib.qe_cpu_c4_mod(row0, n, 42, 3, thr, nkeys, mod, mod, out, 8192, C.byref(ng)) >= 0
+    got = {(o.key,): [o.sum, o.count, o.min, o.max] for o in out[: ng.value]}
+    k, _ = gen.generate(gen.GEN_MOD, nkeys, 42, 0, row0, n)
+    a, _ = gen.generate(gen.GEN_MOD, mod, 42, 1, row0, n)
+    b, _ = gen.generate(gen.GEN_MOD, mod, 42, 2, row0, n)
+    ref = S.group_aggregate([k], [None], [S.arith(S.OP_ADD, a, None, b, None)[0], None, a, b], [None] * 4,
+                            [S.AGG_SUM, S.AGG_COUNT_STAR, S.AGG_MIN, S.AGG_MAX], a > thr)
+    assert len(got) == ng.value == nkeys and got == ref
+    if bits == 20:
+        out0 = (_G * 8192)()
+        ng0 = C.c_int64()
+        assert lib.qe_cpu_c4(row0, n, 42, 3, thr, nkeys, out0, 8192, C.byref(ng0)) >= 0
+        assert {(o.key,): [o.sum, o.count, o.min, o.max] for o in out0[: ng0.value]} == got
 
 
 def test_double_key_equality_semantics():
