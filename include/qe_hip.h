@@ -236,6 +236,46 @@ int qe_filter_apply_async(qe_ctx* ctx, const qe_column* mask, const qe_column* i
 int qe_eval_arith_dlen(qe_ctx* ctx, int32_t op, const qe_operand* lhs, const qe_operand* rhs,
                        qe_column* out, const int64_t* d_len);
 
+/* ---- ORDER BY (build-defined; the reference parses the clause, K:1129-1147, and drops it) ---
+ * Sort keys: 1..QE_MAX_KEYS columns, keys[0] the most significant, one flag word each. Flags 0 =
+ * ascending, nulls last. QE_SORT_NULLS_FIRST places the nulls independently of QE_SORT_DESC, which
+ * reverses only the order of the non-null values.
+ * Order per type: INT64 / INT32 / DATE32 signed, UINT8 unsigned, BOOL false < true; FLOAT64 as
+ * java.lang.Double.compare (-Inf < ... < -0.0 < +0.0 < ... < +Inf < NaN, every NaN bit pattern equal:
+ * the group keys' Double.equals); UTF8 unsigned byte-lexicographic over the UTF-8 bytes (code-point
+ * order; a proper prefix first; 0x00 an ordinary byte).
+ * The sort is STABLE, under DESC too: rows that compare equal on every key keep their input order,
+ * so the result is one permutation, bit-identical from run to run. */
+#define QE_SORT_DESC 1
+#define QE_SORT_NULLS_FIRST 2
+/* Stable multi-key sort -> row indices. keys[0] is the most significant; all keys have the same
+ * length n <= 2^31-1. limit < 0: all rows; limit >= 0: the first min(limit, n) rows of the order.
+ * out_indices: QE_TYPE_INT32, no validity; its length on entry is its row capacity, which must be
+ * >= min(n, limit<0?n:limit) (QE_ERR_CAPACITY); its length is set. A UTF8 key with max_len in 1..7
+ * takes one key word with the bound checked on the device (a longer value: QE_ERR_INVALID_ARG);
+ * other UTF8 keys cost one reduction and read-back for their longest value. Queued on the ctx
+ * stream; above the single-workgroup size (qe_sort_layout) the call reads one digit histogram
+ * back per 64-bit key word, and its working memory (about 2 x 12 bytes per row, from the library's
+ * allocator) is released stream-ordered on return. */
+int qe_sort_indices(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, int32_t nkeys,
+                    int64_t limit, qe_column* out_indices);
+/* outs[c][i] = inputs[c][indices[i]] for fixed-width, BOOL and UTF8 columns (at most 8 per call,
+ * all of one length), validity included. Indices (INT32, no validity) may repeat and come in any
+ * order (a general gather). outs[c].length on entry is the row capacity (>= indices->length); a
+ * validity buffer is written when outs[c] has one (required when inputs[c] has one; whole 32-bit
+ * words). UTF8 outputs need offsets for length+1 entries and a values buffer of at least the sum of
+ * the taken rows' byte lengths: utf8_capacity[c] (host array of ncols entries, read for UTF8
+ * columns only; may be NULL without UTF8 columns) is that buffer's size in bytes. The input's byte
+ * count bounds the sum only when no index repeats. QE_ERR_CAPACITY when the buffer falls short,
+ * decided before any byte is copied.
+ * An index outside [0, inputs.length) reads no memory: its row is written as null (zero where the
+ * output has no validity) and the call returns QE_ERR_INVALID_ARG. Synchronises. */
+int qe_take(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int32_t ncols,
+            qe_column* outs, const int64_t* utf8_capacity);
+/* Measurement hook: rows per tile of the multi-workgroup passes, and the largest n the
+ * single-workgroup path takes. Tests read the boundaries from here. */
+int qe_sort_layout(int32_t* tile_rows, int32_t* small_max);
+
 /* ---- aggregates ------------------------------------------------------------------------- */
 #define QE_AGG_SUM 1
 #define QE_AGG_MIN 2

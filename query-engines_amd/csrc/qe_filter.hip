@@ -366,6 +366,31 @@ __global__ void __launch_bounds__(256) k_copy_bytes(const int2* __restrict__ sl,
   }
 }
 
+// The UTF-8 gather behind qe_filter_apply and qe_take, from `rows` (source byte offset, length) pairs.
+// `tsum` holds 2 * utf8_gather_tiles(rows) + 1 int64: utf8_gather_lengths leaves the per-tile byte
+// sums, their exclusive scan and, in the last entry, the total; utf8_gather_copy then writes the
+// rows + 1 output offsets and copies the bytes.
+int64_t utf8_gather_tiles(int64_t rows) { return (int64_t)div_up((uint64_t)(rows > 0 ? rows : 1), SC_TILE); }
+
+int utf8_gather_lengths(qe_ctx* ctx, const int2* sl, int64_t rows, int64_t* tsum) {
+  const int64_t stiles = utf8_gather_tiles(rows);
+  hipLaunchKernelGGL(k_len_tile_sum, dim3((unsigned)stiles), dim3(256), 0, ctx->stream, sl, rows, tsum);
+  QE_TRY(launch_check("k_len_tile_sum"));
+  return exclusive_scan_i64(ctx, tsum, tsum + stiles, stiles);
+}
+
+int utf8_gather_copy(qe_ctx* ctx, const int2* sl, int64_t rows, const int64_t* tsum, const uint8_t* src,
+                     int32_t* out_offs, uint8_t* out_values) {
+  const int64_t stiles = utf8_gather_tiles(rows);
+  hipLaunchKernelGGL(k_len_tile_scan, dim3((unsigned)stiles), dim3(256), 0, ctx->stream, sl, rows, tsum + stiles, out_offs);
+  QE_TRY(launch_check("k_len_tile_scan"));
+  hipLaunchKernelGGL(k_write_total, dim3(1), dim3(1), 0, ctx->stream, tsum + 2 * stiles, out_offs, rows);
+  QE_TRY(launch_check("k_write_total"));
+  const int64_t grid = std::min<int64_t>((int64_t)div_up((uint64_t)rows, 256), (int64_t)ctx->num_cus * 8);
+  hipLaunchKernelGGL(k_copy_bytes, dim3((unsigned)grid), dim3(256), 0, ctx->stream, sl, out_offs, src, out_values, rows);
+  return launch_check("k_copy_bytes");
+}
+
 struct FilterPlan {
   int64_t ntiles;
   int64_t* counts;   // ntiles
@@ -484,18 +509,9 @@ int qe_filter_apply(qe_ctx* ctx, const qe_column* mask, const qe_column* inputs,
   for (int i = 0; i < ncols && total > 0; ++i) {
     if (args.cols[i].width != 0) continue;
     const int2* sl = (const int2*)args.cols[i].out;
-    hipLaunchKernelGGL(k_len_tile_sum, dim3((unsigned)stiles), dim3(256), 0, ctx->stream, sl, total, tsum);
-    QE_TRY(launch_check("k_len_tile_sum"));
-    QE_TRY(exclusive_scan_i64(ctx, tsum, tsum + stiles, stiles));
-    hipLaunchKernelGGL(k_len_tile_scan, dim3((unsigned)stiles), dim3(256), 0, ctx->stream, sl, total,
-                       tsum + stiles, outs[i].offsets);
-    QE_TRY(launch_check("k_len_tile_scan"));
-    hipLaunchKernelGGL(k_write_total, dim3(1), dim3(1), 0, ctx->stream, tsum + 2 * stiles, outs[i].offsets, total);
-    QE_TRY(launch_check("k_write_total"));
-    const int64_t grid = std::min<int64_t>((int64_t)div_up((uint64_t)total, 256), (int64_t)ctx->num_cus * 8);
-    hipLaunchKernelGGL(k_copy_bytes, dim3((unsigned)grid), dim3(256), 0, ctx->stream, sl, outs[i].offsets,
-                       (const uint8_t*)inputs[i].values, (uint8_t*)outs[i].values, total);
-    QE_TRY(launch_check("k_copy_bytes"));
+    QE_TRY(utf8_gather_lengths(ctx, sl, total, tsum));
+    QE_TRY(utf8_gather_copy(ctx, sl, total, tsum, (const uint8_t*)inputs[i].values, outs[i].offsets,
+                            (uint8_t*)outs[i].values));
   }
   for (int i = 0; i < ncols; ++i)
     if (args.cols[i].width == 0 && total == 0) QE_HIP(hipMemsetAsync(outs[i].offsets, 0, 4, ctx->stream));

@@ -196,6 +196,12 @@ int selproj_rows(const qe::Plan& P, int mode);  // rows per thread of `mode`'s t
 bool selproj_nt(const qe::Plan& P);  // non-temporal input loads (large inputs)
 // Exclusive scan of n int64 on the ctx stream (one block); out[n] = total. (qe_filter.hip)
 int exclusive_scan_i64(qe_ctx* ctx, const int64_t* in, int64_t* out, int64_t n);
+// UTF-8 gather from (source byte offset, length) pairs: length scan, output offsets, byte copy
+// (qe_filter.hip; shared by qe_filter_apply and qe_take).
+int64_t utf8_gather_tiles(int64_t rows);
+int utf8_gather_lengths(qe_ctx* ctx, const int2* sl, int64_t rows, int64_t* tsum);
+int utf8_gather_copy(qe_ctx* ctx, const int2* sl, int64_t rows, const int64_t* tsum, const uint8_t* src,
+                     int32_t* out_offs, uint8_t* out_values);
 
 // ---- type helpers ---------------------------------------------------------------------------
 inline int type_width(int32_t t) {

@@ -389,5 +389,78 @@ class HostColumn(ColumnVector):
         return len(self.array)
 
 
+def _bits_of(buf, n: int):
+    """The first n bits of an LSB-first bitmap tensor, one uint8 (0 / 1) per bit."""
+    import torch
+
+    shifts = torch.arange(8, dtype=torch.uint8, device=buf.device)
+    return ((buf[: (n + 7) // 8].unsqueeze(1) >> shifts) & 1).reshape(-1)[:n]
+
+
+def _pack_bits(bits, n: int):
+    """n bits (uint8 0 / 1) -> an LSB-first bitmap padded with zeros to whole 32-bit words."""
+    import torch
+
+    out = torch.zeros(max(bitmap_bytes(n), 4) * 8, dtype=torch.uint8, device=bits.device)
+    out[:n] = bits
+    weights = torch.tensor([1, 2, 4, 8, 16, 32, 64, 128], dtype=torch.int32, device=bits.device)
+    return (out.reshape(-1, 8).to(torch.int32) * weights).sum(dim=1).to(torch.uint8)
+
+
+def concat_columns(cols: Sequence["DeviceColumn"]) -> "DeviceColumn":
+    """One column holding the rows of `cols` (same type, one device) in order. Torch plumbing for
+    pipeline breakers that need their whole input in one batch (SortExec): bitmaps are re-packed
+    bit by bit, so batch lengths need not be multiples of 8, and UTF8 offsets are rebased onto the
+    concatenated bytes. The result is nullable when any piece is."""
+    import torch
+
+    first = cols[0]
+    ctx, dev, t = first.ctx, first.ctx.torch_device, first.type
+    if any(c.type != t for c in cols):
+        raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG, "concat: the columns differ in type")
+    lens = [c.length for c in cols]
+    n = sum(lens)
+    validity = None
+    if any(c.validity is not None for c in cols):
+        bits = [_bits_of(c.validity, ln) if c.validity is not None else torch.ones(ln, dtype=torch.uint8, device=dev)
+                for c, ln in zip(cols, lens)]
+        validity = _pack_bits(torch.cat(bits), n)
+    offsets = None
+    if t == N.TYPE_BOOL:
+        values = _pack_bits(torch.cat([_bits_of(c.values, ln) for c, ln in zip(cols, lens)]), n)
+    elif t == N.TYPE_UTF8:
+        parts, offs, base = [], [torch.zeros(1, dtype=torch.int64, device=dev)], 0
+        for c, ln in zip(cols, lens):
+            if ln == 0:
+                continue
+            o = c.offsets[: ln + 1].to(torch.int64)
+            lo, hi = int(o[0].item()), int(o[-1].item())
+            parts.append(c.values[lo:hi])
+            offs.append(o[1:] - lo + base)
+            base += hi - lo
+        if base >= 1 << 31:
+            raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "concat: UTF8 bytes exceed int32 offsets")
+        values = torch.cat(parts) if parts else torch.zeros(0, dtype=torch.uint8, device=dev)
+        if values.numel() == 0:
+            values = torch.zeros(1, dtype=torch.uint8, device=dev)
+        offsets = torch.cat(offs).to(torch.int32)
+    else:
+        values = torch.cat([c.values[:ln] for c, ln in zip(cols, lens)])
+        if n == 0:
+            values = torch.zeros(1, dtype=_torch_dtype(t), device=dev)
+    out = DeviceColumn(t, n, values, validity, offsets, ctx)
+    if t == N.TYPE_UTF8 and all(c.max_len is not None for c in cols):
+        out.max_len = max(c.max_len for c in cols)
+    return out
+
+
+def concat_batches(batches: Sequence[RecordBatch]) -> RecordBatch:
+    """The rows of `batches` (one schema, device columns) as ONE batch, in order."""
+    if len(batches) == 1:
+        return batches[0]
+    return RecordBatch(batches[0].schema,
+                       [concat_columns([b.field(i) for b in batches]) for i in range(len(batches[0].fields))])
+
+
 def f64_from_bits(bits: int) -> float:
     return struct.unpack("<d", struct.pack("<q", bits))[0]

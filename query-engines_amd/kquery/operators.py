@@ -210,6 +210,115 @@ def filter_batch(batch: RecordBatch, mask: DeviceColumn) -> RecordBatch:
     return RecordBatch(batch.schema, done)
 
 
+def sort_layout():
+    """(rows per tile of the multi-workgroup sort passes, largest single-workgroup n)."""
+    t, s = N.C.c_int32(), N.C.c_int32()
+    N.check(N.lib().qe_sort_layout(N.C.byref(t), N.C.byref(s)))
+    return t.value, s.value
+
+
+def sort_indices(keys: Sequence[DeviceColumn], flags: Sequence[int], limit: Optional[int] = None) -> DeviceColumn:
+    """qe_sort_indices: the INT32 row indices of the stable order of `keys` (the first key the most
+    significant; flags: N.SORT_DESC | N.SORT_NULLS_FIRST per key), all of them or the first `limit`."""
+    ctx = keys[0].ctx
+    n = keys[0].length
+    lim = -1 if limit is None else int(limit)
+    out = DeviceColumn.empty(N.TYPE_INT32, n if lim < 0 else min(lim, n), False, ctx=ctx)
+    kc = (N.QeColumn * len(keys))(*[k.as_c() for k in keys])
+    fl = (N.C.c_int32 * len(keys))(*[int(f) for f in flags])
+    oc = out.as_c()
+    N.check(N.lib().qe_sort_indices(ctx.handle, kc, fl, len(keys), lim, N.C.byref(oc)))
+    out.length = oc.length
+    return out
+
+
+def take(indices: DeviceColumn, cols: Sequence[DeviceColumn],
+         utf8_bytes: Optional[Sequence[Optional[int]]] = None) -> List[DeviceColumn]:
+    """qe_take: row indices[i] of every column, validity included. utf8_bytes[c]: the value bytes
+    UTF8 output c needs (the sum of the taken lengths); None sizes it as the input's bytes, which
+    is enough when no index repeats."""
+    import torch
+
+    from .columnar import bitmap_bytes
+
+    ctx = indices.ctx
+    m = indices.length
+    dev = ctx.torch_device
+    outs, caps = [], []
+    for i, c in enumerate(cols):
+        if c.type != N.TYPE_UTF8:
+            outs.append(DeviceColumn.empty(c.type, m, c.nullable, ctx=ctx))
+            caps.append(0)
+            continue
+        cap = utf8_bytes[i] if utf8_bytes is not None and utf8_bytes[i] is not None else None
+        if cap is None:
+            cap = int(c.offsets[c.length].item() - c.offsets[0].item()) if c.length else 0
+        outs.append(DeviceColumn(N.TYPE_UTF8, m, torch.empty(max(cap, 1), dtype=torch.uint8, device=dev),
+                                 torch.zeros(max(bitmap_bytes(m), 4), dtype=torch.uint8, device=dev) if c.nullable else None,
+                                 torch.empty(m + 1, dtype=torch.int32, device=dev), ctx))
+        outs[-1].max_len = c.max_len
+        caps.append(cap)
+    ic = indices.as_c()
+    for s in range(0, len(cols), N.MAX_COLS):  # qe_take gathers up to 8 columns per launch
+        part = cols[s:s + N.MAX_COLS]
+        ins = (N.QeColumn * len(part))(*[c.as_c() for c in part])
+        os_ = (N.QeColumn * len(part))(*[o.as_c() for o in outs[s:s + N.MAX_COLS]])
+        cp = (N.C.c_int64 * len(part))(*caps[s:s + N.MAX_COLS])
+        N.check(N.lib().qe_take(ctx.handle, N.C.byref(ic), ins, len(part), os_, cp))
+    return outs
+
+
+class SortExec(PhysicalPlan):
+    """ORDER BY [LIMIT] (build-defined; the reference parses the clause and drops it,
+    Main.kt:1129-1147). A pipeline breaker like HashAggregateExec: drains its input into one batch
+    (concat_batches), evaluates the sort expressions, sorts to row indices (qe_sort_indices: stable,
+    DESIGN §4) and gathers every column by them (qe_take). sort_exprs: (Expression, ascending,
+    nulls_first) triples, the first the most significant. Yields ONE batch with the input's schema;
+    an empty input gives a 0-row batch."""
+
+    def __init__(self, input: PhysicalPlan, sort_exprs, limit: Optional[int] = None):  # noqa: A002
+        if not sort_exprs or len(sort_exprs) > N.MAX_KEYS:
+            raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG, f"ORDER BY takes 1..{N.MAX_KEYS} expressions")
+        if limit is not None and limit < 0:
+            raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG, "LIMIT must not be negative")
+        self.input = input
+        self.sort_exprs = [(e, bool(asc), bool(nf)) for e, asc, nf in sort_exprs]
+        self.limit = limit
+
+    def schema(self) -> Schema:
+        return self.input.schema()
+
+    def children(self) -> List[PhysicalPlan]:
+        return [self.input]
+
+    def execute(self) -> Iterator[RecordBatch]:
+        from .columnar import Context, concat_batches
+
+        schema = self.schema()
+        batches = [b for b in self.input.execute() if b.fields]
+        for b in batches:
+            for c in b.fields:
+                if not isinstance(c, DeviceColumn):
+                    raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "sort input must be device columns")
+        if not batches:
+            ctx = Context.get(0)
+            yield RecordBatch(schema, [
+                DeviceColumn.from_strings([], ctx=ctx) if f.dataType == N.TYPE_UTF8
+                else DeviceColumn.empty(f.dataType, 0, True, ctx=ctx) for f in schema.fields])
+            return
+        batch = concat_batches(batches)
+        keys = [e.evaluate(batch) for e, _, _ in self.sort_exprs]
+        for k in keys:
+            if not isinstance(k, DeviceColumn):
+                raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "a sort expression must evaluate to a column")
+        flags = [(0 if asc else N.SORT_DESC) | (N.SORT_NULLS_FIRST if nf else 0) for _, asc, nf in self.sort_exprs]
+        idx = sort_indices(keys, flags, self.limit)
+        yield RecordBatch(schema, take(idx, batch.fields))
+
+    def __repr__(self) -> str:
+        return f"SortExec: {self.sort_exprs}, limit={self.limit}"
+
+
 class HashAggregateExec(PhysicalPlan):
     """Main.kt:605-660: consumes every input batch, emits ONE batch of group columns then
     aggregate columns. Row-at-a-time HashMap + Accumulator objects are replaced by the device
