@@ -34,7 +34,6 @@
 namespace qe {
 
 constexpr int HA_THREADS = 512;
-constexpr size_t HA_LDS_BUDGET = 80 * 1024;  // bytes of LDS per workgroup (2 workgroups / CU)
 
 // ---- LDS table -----------------------------------------------------------------------------------
 __device__ __forceinline__ qi64* lds_keys(char* smem) { return (qi64*)smem; }
@@ -805,7 +804,6 @@ __global__ void __launch_bounds__(1024) k_part_slices(const qi64* __restrict__ o
 //   k_chunk_place  chunk ids grouped by bucket into `sorted` (per-workgroup LDS ranks, one global
 //                  atomic per (workgroup, bucket) on cur; order inside a bucket is arbitrary)
 // cnt, rec and cur are zeroed by the caller.
-constexpr int CHUNK_PLAN_MAXB = 512;  // buckets of the staged scatter
 constexpr int CHUNK_PER_WG = 1024;    // chunks per workgroup of k_chunk_hist / k_chunk_place
 __global__ void __launch_bounds__(256) k_chunk_hist(const qi64* __restrict__ meta, qi32 np, qu32* __restrict__ cnt,
                                                    unsigned long long* __restrict__ rec) {
@@ -1571,11 +1569,7 @@ static AggMeta agg_meta(const qe_hashagg* h) {
 // nn atomics (3 of the C4 flush's 7 per group) — and anything that adds real counts makes it
 // explicit first.
 static int32_t all_nn_bits(const qe_hashagg* h) {
-  static const bool off = [] {  // QE_NN_IMPLICIT=0: always store the counts (A/B and debugging)
-    const char* e = getenv("QE_NN_IMPLICIT");
-    return e && e[0] == '0';
-  }();
-  if (off) return 0;
+  if (!agg_knobs().nn_implicit) return 0;
   int32_t b = 0;
   for (int j = 0; j < h->naggs; ++j)
     if (h->aggs[j].fn != QE_AGG_COUNT_STAR) b |= 1 << j;
@@ -1899,78 +1893,23 @@ static int compile_plan(qe_hashagg* h, const qe_column* cols, int32_t ncols, con
   return QE_OK;
 }
 
-// LDS layout for a table of 2^log2 slots under this launch's aggregates. Returns bytes.
-// LDS words per slot beyond acc of an aggregate with idx arrays: fp64 MIN / MAX keep 4 row
-// indices; an exact fp64 SUM keeps 4 more words (256-bit + status) in the generic kernel, and in
-// the plan-specialised kernels 5 (limb window, qe_dev.hpp fxl_add) or 2 (192-bit window, fxw_add);
-// rare rows go global.
-static size_t idx_words(int acc, bool generic) {
-  return acc == ACC_SUM_X && !generic ? (size_t)fx_window_idx_words() : 4;
-}
-
+// LDS layout of a 2^log2-slot table under this launch's aggregates (qe_agg_paths.hpp), the generic
+// kernel's when the context does not specialise.
 static size_t lds_layout_at(const qe_hashagg* h, Plan* P, int log2, bool generic = false) {
-  generic = generic || !h->ctx->jit;
-  const size_t SS = ((size_t)1 << log2) + 2;
-  size_t off = 8 * SS;  // keys
-  P->off_cstar = (int32_t)off;
-  off += 4 * SS;
-  off = (off + 15) & ~size_t(15);
-  for (int j = 0; j < h->naggs; ++j) {
-    const DAgg& a = P->aggs[j];
-    if (!generic && a.share) continue;  // the specialised kernels read the shared accumulator
-    if (a.acc != ACC_NONE) {
-      P->off_acc[j] = (int32_t)off;
-      off += 8 * SS;
-    }
-    if (a.track_nn) {
-      P->off_nn[j] = (int32_t)off;
-      off += 4 * SS;
-      off = (off + 15) & ~size_t(15);
-    }
-    if (acc_has_idx(a.acc)) {
-      P->off_idx[j] = (int32_t)off;
-      off += 8 * idx_words(a.acc, generic) * SS;
-    }
-  }
-  P->lds_log2 = log2;
-  return off;
+  return lds_table_layout(P, h->naggs, log2, generic || !h->ctx->jit);
 }
 
-// LDS bytes a workgroup's table may take. The generic kernel runs two 512-thread workgroups per
-// CU (80 KiB each). The specialised kernel's 1024-thread workgroups run one per CU, so its table
-// may take nearly all of the CU's 160 KiB: twice the groups in one pass (C4 shape: up to ~2.5K
-// groups in a 4096-slot table instead of ~1.3K in 2048 slots). QE_LDS_BUDGET_KB overrides.
-static size_t lds_budget(const qe_ctx* ctx) {
-  static const size_t env = [] {
-    const char* e = getenv("QE_LDS_BUDGET_KB");
-    return e && *e ? (size_t)std::max(16, std::min(156, atoi(e))) * 1024 : (size_t)0;
-  }();
-  if (env) return env;
-  return (ctx->jit && fused_block(0) == 1024) ? (size_t)152 * 1024 : HA_LDS_BUDGET;
-}
+static size_t lds_budget(const qe_ctx* ctx) { return fused_lds_budget(agg_knobs(), ctx->jit, fused_block(0)); }
 
 // Largest LDS table in [lds_log2_min, lds_log2] that fits the per-workgroup budget; 0 bytes =>
 // global-only launch (the expected groups do not fit on chip).
 static size_t lds_layout(const qe_hashagg* h, Plan* P) {
-  if (h->lds_log2 == 0) return 0;
-  const size_t budget = lds_budget(h->ctx);
-  for (int log2 = h->lds_log2; log2 >= h->lds_log2_min; --log2) {
-    const size_t b = lds_layout_at(h, P, log2);
-    if (b <= budget) return b;
-  }
-  P->lds_log2 = 0;
-  return 0;
+  return lds_regular_layout(P, h->naggs, LdsRange{h->lds_log2, h->lds_log2_min}, !h->ctx->jit, lds_budget(h->ctx));
 }
 
-// LDS bytes with no nullable inputs (the smallest layout a launch can have).
-static size_t lds_bytes_min(const qe_hashagg* h, int log2) {
-  const size_t SS = ((size_t)1 << log2) + 2;
-  size_t b = 12 * SS + 16;
-  for (int j = 0; j < h->naggs; ++j) {
-    if (h->acc[j] != ACC_NONE) b += 8 * SS;
-    if (acc_has_idx(h->acc[j])) b += 8 * idx_words(h->acc[j], !h->ctx->jit) * SS;
-  }
-  return b;
+// log2 of the largest table of at most 2^16 slots within `budget`, P laid out for it; < 8: none fits.
+static int largest_table(const qe_hashagg* h, Plan* P, size_t budget) {
+  return largest_table_log2(budget, [&](int log2) { return lds_layout_at(h, P, log2); });
 }
 
 template <int NC>
@@ -2009,6 +1948,51 @@ static int grow_buffer(T** p, size_t* have, size_t need, qe_ctx* ctx, const char
   return QE_OK;
 }
 
+// Overflow records of the launches to come: at least `records` of them.
+static int ensure_overflow(qe_hashagg* h, uint64_t records) {
+  if (h->ovf && h->ovf_cap >= records) return QE_OK;
+  dev_free(h->ctx, h->ovf);
+  h->ovf = nullptr;
+  h->ovf_cap = 0;
+  QE_TRY(dev_alloc(h->ctx, records * h->rec_bytes, (void**)&h->ovf));
+  h->ovf_cap = records;
+  return QE_OK;
+}
+
+// The chunk table's parts (qe_agg_paths.hpp chunk_table) in the state's part_cnt allocation.
+struct ChunkPtrs {
+  qi64* meta;
+  qi32* sorted;
+  unsigned long long* prec;
+  qu32 *pcnt, *pcur, *pbase;
+};
+static ChunkPtrs chunk_ptrs(qe_hashagg* h, const ChunkTable& t) {
+  uint8_t* b = (uint8_t*)h->part_cnt;
+  return {(qi64*)(b + t.meta), (qi32*)(b + t.sorted), (unsigned long long*)(b + t.prec),
+          (qu32*)(b + t.pcnt), (qu32*)(b + t.pcur), (qu32*)(b + t.pbase)};
+}
+
+// Chunks written (up to `chunks` ids), grouped by their `buckets` buckets and cut into at most
+// tmax + buckets aggregation slices (k_chunk_hist / k_chunk_slices / k_chunk_place above). The
+// planning counters prec, pcnt and pcur are zeroed by the caller.
+static int plan_chunks(qe_hashagg* h, const ChunkPtrs& c, int64_t chunks, int64_t buckets, int64_t tmax) {
+  hipStream_t st = h->ctx->stream;
+  const unsigned pg = (unsigned)div_up((uint64_t)chunks, CHUNK_PER_WG);
+  hipLaunchKernelGGL(k_chunk_hist, dim3(pg), dim3(256), 0, st, (const qi64*)c.meta, (qi32)buckets, c.pcnt, c.prec);
+  QE_TRY(launch_check("k_chunk_hist"));
+  hipLaunchKernelGGL(k_chunk_slices, dim3(1), dim3(1024), 0, st, (const qi64*)c.meta, (qi32)buckets, (qi64)tmax,
+                     (const qu32*)c.pcnt, (const unsigned long long*)c.prec, (qi64*)h->part_slc, c.pbase);
+  QE_TRY(launch_check("k_chunk_slices"));
+  hipLaunchKernelGGL(k_chunk_place, dim3(pg), dim3(256), 0, st, (const qi64*)c.meta, (qi32)buckets, (const qu32*)c.pbase,
+                     c.pcur, c.sorted);
+  return launch_check("k_chunk_place");
+}
+
+// "... B (" + this: how the words of a record are stored
+static std::string record_words_note(const PartLayout& L) {
+  return std::string(L.colmode ? "column" : "value") + (L.narrow ? " words, 32-bit)" : " words)");
+}
+
 // Radix-partitioned update, steps 1-3 (qe_jit.hip, "radix-partitioned aggregation"): count the
 // selected rows per (key-hash bucket, workgroup), scan, scatter one record per selected row into
 // its bucket. On return P describes the aggregation pass over the records (P.n = records,
@@ -2016,92 +2000,23 @@ static int grow_buffer(T** p, size_t* have, size_t need, qe_ctx* ctx, const char
 // Narrow records (QE_PART_NARROW, default 1): integral record words are stored as 32 bits while
 // every value of the update fits (sign-extended); the scatter flags ctl[7] otherwise, the
 // aggregation pass then does nothing and run_update repeats the update with 64-bit words.
-static bool part_narrow_env() {
-  static const bool v = [] {
-    const char* e = getenv("QE_PART_NARROW");
-    return !(e && e[0] == '0');
-  }();
-  return v;
-}
-
-static int partition_rows(qe_hashagg* h, Plan& P, hipFunction_t* fn, int* grid) {
+// tlog2: the aggregation pass's LDS table (the ladder's PATH_PARTITION rung).
+static int partition_rows(qe_hashagg* h, Plan& P, int tlog2, const AggKnobs& K, hipFunction_t* fn, int* grid) {
   qe_ctx* ctx = h->ctx;
-  P.part_narrow = (!h->part_wide && part_narrow_env() && !part_soa()) ? 1 : 0;
+  P.part_narrow = (!h->part_wide && K.part_narrow && !part_soa()) ? 1 : 0;
   P.t = h->t;  // the scatter's fit flag (t.ctl[7])
-  // aggregation-pass LDS table: the largest that fits the per-workgroup budget
-  int tlog2 = 16;
-  const size_t pbudget = pagg_block() == 1024 ? (size_t)152 * 1024 : HA_LDS_BUDGET;
-  while (tlog2 >= 8 && lds_layout_at(h, &P, tlog2) > pbudget) --tlog2;
   QE_CHECK(tlog2 >= 8, QE_ERR_UNSUPPORTED, "aggregate state too wide for a partitioned LDS table");
-  // buckets: about a quarter of the table's slots in groups per bucket while that takes <= 64
-  // buckets, half the slots beyond (a slice spans <= 2 buckets; QE_PART_FILL_SHIFT = 1 / 2 fixes
-  // half / a quarter). 1B rows, C4 shape, half-full against quarter-full tables: 65,536 groups
-  // 13.66 vs 13.50 ms, 262,144 14.87 vs 15.78, 1,048,576 (512 staged buckets instead of 1024
-  // direct) 19.1 vs 19.3, 4,194,304 20.9 vs 21.2, 16,777,216 27.6 vs 27.7.
-  static const int fill_env = [] {
-    const char* e = getenv("QE_PART_FILL_SHIFT");
-    const int v = e && *e ? atoi(e) : 0;
-    return v >= 1 && v <= 3 ? v : 0;
-  }();
-  auto buckets_log2 = [&](int shift) {
-    int l = 1;
-    while (l < 13 && (((int64_t)1 << tlog2) >> shift) * ((int64_t)1 << l) < h->expected_groups) ++l;
-    return l;
-  };
-  int log2p = fill_env ? buckets_log2(fill_env) : buckets_log2(2);
-  if (!fill_env && log2p > 6) log2p = buckets_log2(1);
-  // QE_PART_FAST_FILL (percent): buckets for the fast aggregation pass's own (larger) table, each
-  // bucket's expected groups at most that share of its slots (fewer buckets: longer scatter runs)
-  static const int fast_fill = [] {
-    const char* e = getenv("QE_PART_FAST_FILL");
-    const int v = e && *e ? atoi(e) : 0;
-    return v >= 10 && v <= 90 ? v : 0;
-  }();
-  if (!fill_env && fast_fill) {
-    const int64_t fs = (int64_t)pagg_fast_slots(P) * fast_fill / 100;
-    if (fs > 0) {
-      int l = 1;
-      while (l < 13 && fs * ((int64_t)1 << l) < h->expected_groups) ++l;
-      log2p = l;
-    }
-  }
+  lds_layout_at(h, &P, tlog2);
+  const int log2p = part_buckets_log2(tlog2, h->expected_groups, K.part_fast_fill ? pagg_fast_slots(P) : 0, K);
   std::string sc, ss, sa;
   size_t jl = 0;
   const bool staged = part_staged_ok(P, log2p);
   const int sblock = staged ? pscatter_block_for(log2p) : 512;
-  const int64_t n = P.n;
-  // count / scatter workgroups per CU (QE_PART_WG_PER_CU overrides; see pscatter_block)
-  static const int wg_per_cu = [] {
-    const char* e = getenv("QE_PART_WG_PER_CU");
-    const int v = e && *e ? atoi(e) : 2;
-    return v >= 1 && v <= 32 ? v : 2;
-  }();
-  // (one 1024-thread staged workgroup fits a CU)
-  int64_t g = std::min<int64_t>((int64_t)ctx->num_cus * (sblock == 1024 ? 1 : wg_per_cu), (int64_t)div_up((uint64_t)n, 256));
   const PartLayout L = part_layout(P);
   const size_t rb = (size_t)L.bytes();
+  const PartGeometry G = part_geometry(P.n, ctx->num_cus, log2p, staged, sblock, rb, K);
+  const bool chunked = G.chunked;
   if (L.narrow) QE_HIP(hipMemsetAsync(h->ctl + 7, 0, 8, ctx->stream));
-  // Chunked scatter (staged buckets): no count pass and no read-back of the record count;
-  // workgroups claim PART_CH-record chunks per bucket from a device counter. Record space: every
-  // selected row in a full chunk plus one open chunk per (workgroup, bucket) — at most
-  // n / PART_CH + g x buckets chunks — so it is taken while the open chunks' slots do not exceed
-  // the batch's rows (large batches). QE_PART_CHUNKED (read per call): 0 never, 1 whenever the
-  // scatter is staged, unset: by that rule.
-  // (forced on a small batch, the scatter runs fewer workgroups so that the open chunks stay
-  // within 4x the rows: tests exercise the chunked path at their sizes)
-  const char* ce = getenv("QE_PART_CHUNKED");
-  const int chunk_env = ce && *ce ? (ce[0] == '0' ? 0 : 1) : -1;
-  const int64_t np_all = (int64_t)1 << log2p;
-  if (chunk_env == 1 && staged && g * np_all * PART_CH > 4 * n)
-    g = std::max<int64_t>(1, 4 * n / (np_all * PART_CH));
-  const int64_t tw = (int64_t)div_up(div_up((uint64_t)n, (uint64_t)g), 256) * 256;
-  g = (int64_t)div_up((uint64_t)n, (uint64_t)tw);
-  const int64_t open_slots = g * np_all * PART_CH;
-  // chunk ids: every claim of a device-wide counter, or each workgroup's own range (part_static)
-  const int64_t cmax = std::max<int64_t>((int64_t)div_up((uint64_t)n, (uint64_t)PART_CH) + g * np_all + 1,
-                                         g * ((int64_t)div_up((uint64_t)tw, (uint64_t)PART_CH) + np_all));
-  const bool chunked = chunk_env != 0 && staged && np_all <= CHUNK_PLAN_MAXB &&
-                       (chunk_env == 1 || open_slots <= n) && (uint64_t)cmax * PART_CH * rb <= (96ull << 30);
   QE_CHECK((chunked || gen_part_source(P, log2p, false, &sc)) &&
                (staged ? gen_pscatter_staged_source(P, log2p, &ss, chunked, chunked && part_soa())
                        : gen_part_source(P, log2p, true, &ss)) &&
@@ -2113,117 +2028,67 @@ static int partition_rows(qe_hashagg* h, Plan& P, hipFunction_t* fn, int* grid) 
   if (!chunked) QE_TRY(jit_kernel(ctx, sc, &fc, &bpc, "qe_pcount"));
   QE_TRY(jit_kernel(ctx, ss, &fs, &bpc, "qe_pscatter", sblock));
   QE_TRY(jit_kernel(ctx, sa, fn, &bpc, "qe_pagg", pagg_block()));
+  P.part_tw = G.tw;
   if (chunked) {
-    const int64_t np = (int64_t)1 << log2p;
-    // [0] chunks claimed | per chunk (bucket << 32 | records) | chunk ids by bucket (int32)
-    // chunk table | sorted chunk ids | plan scratch: cnt u32[np], cur u32[np], base u32[np], rec u64[np]
-    const size_t tbl = ((size_t)(1 + cmax) * 8 + (size_t)cmax * 4 + 7) & ~(size_t)7;
-    QE_TRY(grow_buffer(&h->part_cnt, &h->part_cnt_bytes, tbl + (size_t)np * 20, ctx, "chunk table"));
-    qi64* meta = (qi64*)h->part_cnt;
-    qi32* sorted = (qi32*)(meta + 1 + cmax);
-    unsigned long long* prec = (unsigned long long*)((uint8_t*)h->part_cnt + tbl);
-    qu32* pcnt = (qu32*)(prec + np);
-    qu32* pcur = pcnt + np;
-    qu32* pbase = pcur + np;
-    QE_TRY(grow_buffer(&h->part_rec, &h->part_rec_bytes, (size_t)cmax * PART_CH * rb, ctx, "partition records"));
-    // aggregation slices: at most QE_PAGG_SLICES_PER_CU (default 8) per CU. One 1024-thread
-    // workgroup runs per CU either way; more slices balance better, fewer flush less (each slice
-    // of a bucket flushes every group it saw with device-scope atomics)
-    static const int spc = [] {
-      const char* e = getenv("QE_PAGG_SLICES_PER_CU");
-      const int v = e && *e ? atoi(e) : 8;
-      return v >= 1 && v <= 64 ? v : 8;
-    }();
-    const int64_t tmax = (int64_t)ctx->num_cus * spc;
-    const int64_t max_slices = tmax + np;
-    QE_TRY(grow_buffer(&h->part_slc, &h->part_slc_bytes, (size_t)(2 + 2 * max_slices) * 8, ctx, "partition slices"));
-    if (!h->ovf || h->ovf_cap < (1ull << 20)) {
-      uint8_t* ovf = nullptr;
-      size_t have = 0;
-      QE_TRY(grow_buffer(&ovf, &have, (size_t)(1ull << 20) * h->rec_bytes, ctx, "overflow area"));
-      dev_free(ctx, h->ovf);
-      h->ovf = ovf;
-      h->ovf_cap = 1ull << 20;
-    }
-    QE_TRY(ensure_defer(h, cmax * PART_CH));  // the retry bitmaps index record slots
+    QE_TRY(grow_buffer(&h->part_cnt, &h->part_cnt_bytes, G.table.bytes, ctx, "chunk table"));
+    const ChunkPtrs C = chunk_ptrs(h, G.table);
+    QE_TRY(grow_buffer(&h->part_rec, &h->part_rec_bytes, G.rec_bytes, ctx, "partition records"));
+    QE_TRY(grow_buffer(&h->part_slc, &h->part_slc_bytes, G.slice_bytes, ctx, "partition slices"));
+    QE_TRY(ensure_overflow(h, PART_OVF_RECORDS));
+    QE_TRY(ensure_defer(h, G.rec_slots));  // the retry bitmaps index record slots
     P.ovf = h->ovf;
     P.ovf_cap = h->ovf_cap;
-    QE_HIP(hipMemsetAsync(meta, 0, 8, ctx->stream));
-    QE_HIP(hipMemsetAsync(prec, 0, (size_t)np * 16, ctx->stream));  // rec, cnt, cur
-    P.part_tw = tw;
+    QE_HIP(hipMemsetAsync(C.meta, 0, 8, ctx->stream));
+    QE_HIP(hipMemsetAsync(C.prec, 0, (size_t)G.np * 16, ctx->stream));  // rec, cnt, cur
     P.part_rec = h->part_rec;
-    P.part_chunk = meta;
-    h->chunk_cap = cmax;
-    QE_TRY(jit_launch(ctx, fs, (int)g, P, sblock));
+    P.part_chunk = C.meta;
+    h->chunk_cap = G.cmax;
+    QE_TRY(jit_launch(ctx, fs, (int)G.g, P, sblock));
     QE_TRY(launch_check("qe_pscatter"));
-    const unsigned pg = (unsigned)div_up((uint64_t)cmax, CHUNK_PER_WG);
-    hipLaunchKernelGGL(k_chunk_hist, dim3(pg), dim3(256), 0, ctx->stream, (const qi64*)meta, (qi32)np, pcnt, prec);
-    QE_TRY(launch_check("k_chunk_hist"));
-    hipLaunchKernelGGL(k_chunk_slices, dim3(1), dim3(1024), 0, ctx->stream, (const qi64*)meta, (qi32)np, (qi64)tmax,
-                       (const qu32*)pcnt, (const unsigned long long*)prec, (qi64*)h->part_slc, pbase);
-    QE_TRY(launch_check("k_chunk_slices"));
-    hipLaunchKernelGGL(k_chunk_place, dim3(pg), dim3(256), 0, ctx->stream, (const qi64*)meta, (qi32)np,
-                       (const qu32*)pbase, pcur, sorted);
-    QE_TRY(launch_check("k_chunk_place"));
-    P.n = cmax * PART_CH;
+    QE_TRY(plan_chunks(h, C, G.cmax, G.np, G.tmax));
+    P.n = G.rec_slots;
     P.part_slice = (qi64*)h->part_slc;
-    P.part_sorted = sorted;
-    *grid = (int)max_slices;
-    h->jit_note = "radix-partitioned: " + std::to_string(np) + " buckets, chunked records of " + std::to_string(rb) +
-                  " B (" + (L.colmode ? "column" : "value") + (L.narrow ? " words, 32-bit" : " words") + "), staged scatter";
+    P.part_sorted = C.sorted;
+    *grid = (int)G.max_slices;
+    h->jit_note = "radix-partitioned: " + std::to_string(G.np) + " buckets, chunked records of " + std::to_string(rb) +
+                  " B (" + record_words_note(L) + ", staged scatter";
     return QE_OK;
   }
-  const size_t cells = ((size_t)1 << log2p) * (size_t)g;
-  QE_TRY(grow_buffer(&h->part_cnt, &h->part_cnt_bytes, (2 * cells + 1) * 8, ctx, "partition counts"));
+  QE_TRY(grow_buffer(&h->part_cnt, &h->part_cnt_bytes, G.count_bytes, ctx, "partition counts"));
   int64_t* cnt = h->part_cnt;
-  int64_t* off = cnt + cells;
-  P.part_tw = tw;
+  int64_t* off = cnt + G.cells;
   P.part_off = (qi64*)cnt;
-  QE_TRY(jit_launch(ctx, fc, (int)g, P));
+  QE_TRY(jit_launch(ctx, fc, (int)G.g, P));
   QE_TRY(launch_check("qe_pcount"));
-  QE_TRY(exclusive_scan_i64(ctx, cnt, off, (int64_t)cells));
+  QE_TRY(exclusive_scan_i64(ctx, cnt, off, (int64_t)G.cells));
   void* pin;
   QE_TRY(ctx_pinned(ctx, 8, &pin));
-  QE_HIP(hipMemcpyAsync(pin, off + cells, 8, hipMemcpyDeviceToHost, ctx->stream));
+  QE_HIP(hipMemcpyAsync(pin, off + G.cells, 8, hipMemcpyDeviceToHost, ctx->stream));
   QE_TRY(ctx_sync(ctx));
   const int64_t R = *(int64_t*)pin;
   // overflow records of the aggregation pass (bounded; groups beyond it retry their records)
-  if (!h->ovf || h->ovf_cap < (1ull << 20)) {
-    uint8_t* ovf = nullptr;
-    size_t have = 0;
-    QE_TRY(grow_buffer(&ovf, &have, (size_t)(1ull << 20) * h->rec_bytes, ctx, "overflow area"));
-    dev_free(ctx, h->ovf);
-    h->ovf = ovf;
-    h->ovf_cap = 1ull << 20;
-  }
+  QE_TRY(ensure_overflow(h, PART_OVF_RECORDS));
   P.ovf = h->ovf;
   P.ovf_cap = h->ovf_cap;
   if (R > 0) {
     QE_TRY(grow_buffer(&h->part_rec, &h->part_rec_bytes, (size_t)R * rb, ctx, "partition records"));
     P.part_off = (qi64*)off;
     P.part_rec = h->part_rec;
-    QE_TRY(jit_launch(ctx, fs, (int)g, P, sblock));
+    QE_TRY(jit_launch(ctx, fs, (int)G.g, P, sblock));
     QE_TRY(launch_check("qe_pscatter"));
   }
-  // aggregation slices inside bucket boundaries: one per bucket, or more (up to 8 per CU, none
-  // below ~32K records) when there are few buckets; cw is 5/4 of the even share, so a bucket of
-  // about average size is one slice, whose workgroup then owns its groups outright (plain
-  // combines, k_part_slices)
-  const int64_t target = std::max<int64_t>((int64_t)1 << log2p, std::min<int64_t>((int64_t)ctx->num_cus * 8, R >> 15));
-  const int64_t cw = std::max<int64_t>(256, (int64_t)div_up((uint64_t)std::max<int64_t>(R, 1) * 5, (uint64_t)target * 4));
-  const int64_t max_slices = ((int64_t)1 << log2p) + (int64_t)div_up((uint64_t)std::max<int64_t>(R, 1), (uint64_t)cw);
-  QE_TRY(grow_buffer(&h->part_slc, &h->part_slc_bytes, (size_t)(2 + 2 * max_slices) * 8, ctx, "partition slices"));
-  hipLaunchKernelGGL(k_part_slices, dim3(1), dim3(1024), 0, ctx->stream, (const qi64*)off, (qi32)(1 << log2p), (qi64)g,
-                     (qi64)cw, (qi64*)h->part_slc);
+  const CountedSlices S = counted_slices(R, G.np, ctx->num_cus);
+  QE_TRY(grow_buffer(&h->part_slc, &h->part_slc_bytes, S.slice_bytes, ctx, "partition slices"));
+  hipLaunchKernelGGL(k_part_slices, dim3(1), dim3(1024), 0, ctx->stream, (const qi64*)off, (qi32)G.np, (qi64)G.g,
+                     (qi64)S.cw, (qi64*)h->part_slc);
   QE_TRY(launch_check("k_part_slices"));
   P.n = R;
-  P.part_tw = cw;
+  P.part_tw = S.cw;
   P.part_rec = h->part_rec;
   P.part_slice = (qi64*)h->part_slc;
-  *grid = (int)max_slices;
-  h->jit_note = "radix-partitioned: " + std::to_string(1 << log2p) + " buckets, " + std::to_string(R) + " records of " +
-                std::to_string(rb) + " B (" + (L.colmode ? "column" : "value") + (L.narrow ? " words, 32-bit)" : " words)") +
-                (staged ? ", staged scatter" : "");
+  *grid = (int)S.max_slices;
+  h->jit_note = "radix-partitioned: " + std::to_string(G.np) + " buckets, " + std::to_string(R) + " records of " +
+                std::to_string(rb) + " B (" + record_words_note(L) + (staged ? ", staged scatter" : "");
   return QE_OK;
 }
 
@@ -2290,10 +2155,7 @@ static int launch_pass(qe_hashagg* h, Plan& P, size_t& lds, hipFunction_t pfn, i
           std::lock_guard<std::mutex> g(memo_mu);
           memo[key] = {jfn, bpc};
         }
-        static const int wg_env = [] {  // QE_FUSED_WG_PER_CU: workgroups per CU (default: the state's)
-          const char* e = getenv("QE_FUSED_WG_PER_CU");
-          return e && *e ? std::max(1, atoi(e)) : 0;
-        }();
+        const int wg_env = agg_knobs().fused_wg_per_cu;  // QE_FUSED_WG_PER_CU: workgroups per CU (default: the state's)
         const int64_t per_state = wg_env ? (int64_t)ctx->num_cus * wg_env
                                          : std::max<int64_t>(ctx->num_cus, h->grid * 512 / fused_block(P.lds_log2));
         jgrid = (int)std::min<int64_t>(std::min<int64_t>((int64_t)ctx->num_cus * bpc, per_state),
@@ -2436,11 +2298,18 @@ static int settle_pending(qe_hashagg* h) {
   return st;
 }
 
-// Kept share of the spilling pass in eighths of the kept table's slots (QE_SPILL_LOAD, 4..7, read
-// per call; default 6).
-static int spill_load8() {
-  const char* le = getenv("QE_SPILL_LOAD");
-  return le && *le ? std::max(4, std::min(7, atoi(le))) : 6;
+// Passes of one kernel over P until nothing is left deferred. *misfit: a pass saw a value outside
+// the 32-bit records.
+static int run_passes(qe_hashagg* h, Plan& P, size_t& lds, hipFunction_t fn, int grid, int mp, int* out_i, int block = 0,
+                      bool* misfit = nullptr) {
+  const uint32_t* defer_in = nullptr;
+  for (int pass = 0;; ++pass) {
+    QE_TRY(launch_pass(h, P, lds, fn, grid, pass, mp, *out_i, defer_in, block));
+    bool done = false;
+    QE_TRY(settle_pass(h, P, out_i, &defer_in, &done));
+    if (misfit) *misfit = *misfit || h->narrow_failed;
+    if (done) return QE_OK;
+  }
 }
 
 // Two key-hash buckets (groups just beyond one LDS table; QE_MP_SPILL, read per call, 0 = two
@@ -2449,25 +2318,21 @@ static int spill_load8() {
 // k_spill_plan slices them (at most a slice per CU) and one chunked qe_pagg pass aggregates bucket 1. The columns are read once: C4 shape
 // 24 B/row + 2 x 24 B per spilled record (~36 GB at 1B rows) instead of 48 B/row for two passes.
 // *used = false: not applicable here (the caller runs the fused passes).
-static int spill_update(qe_hashagg* h, Plan& P, size_t lds, int64_t rows, bool* used) {
+static int spill_update(qe_hashagg* h, Plan& P, size_t lds, int64_t rows, const AggKnobs& K, bool* used) {
   qe_ctx* ctx = h->ctx;
   *used = false;
-  const char* e = getenv("QE_MP_SPILL");
-  if ((e && e[0] == '0') || P.mp_n < 2) return QE_OK;
-  const int SB = P.mp_n - 1;  // sub-buckets of the spilled share (a power of two, <= 8)
-  if (SB > 8 || (SB & (SB - 1))) return QE_OK;
-  P.part_narrow = (!h->part_wide && part_narrow_env()) ? 1 : 0;  // 32-bit record words while values fit
+  const int SB = spill_sub_buckets(K, P.mp_n);
+  if (!SB) return QE_OK;
+  P.part_narrow = (!h->part_wide && K.part_narrow) ? 1 : 0;  // 32-bit record words while values fit
   P.t = h->t;
   const PartLayout L = part_layout(P);
   const size_t rb = (size_t)L.bytes();
-  if ((uint64_t)rows * rb > (96ull << 30)) return QE_OK;
+  if ((uint64_t)rows * rb > PART_REC_MAX_BYTES) return QE_OK;
   Plan Q = P;
   Q.mp_n = 0;
   Q.mp_pass = 0;
   Q.lds_compact = 0;  // (the spilled records' pass keeps the regular table)
-  int tlog2 = 16;
-  const size_t pbudget = pagg_block() == 1024 ? (size_t)152 * 1024 : HA_LDS_BUDGET;
-  while (tlog2 >= 8 && lds_layout_at(h, &Q, tlog2) > pbudget) --tlog2;
+  const int tlog2 = largest_table(h, &Q, pagg_lds_budget(pagg_block()));
   if (tlog2 < 8) return QE_OK;
   std::string ss, sa;
   size_t jl = 0;
@@ -2478,52 +2343,25 @@ static int spill_update(qe_hashagg* h, Plan& P, size_t lds, int64_t rows, bool* 
   const int sblock = fused_block(P.lds_log2);
   QE_TRY(jit_kernel(ctx, ss, &fs, &bpc, "qe_fused", sblock));
   QE_TRY(jit_kernel(ctx, sa, &fa, &bpc_a, "qe_pagg", pagg_block()));
-  const int64_t waves = (int64_t)div_up((uint64_t)rows, 256);
-  const int sgrid = (int)std::max<int64_t>(
-      1, std::min<int64_t>((int64_t)ctx->num_cus * std::max(1, bpc), (int64_t)div_up((uint64_t)waves, sblock / 64)));
-  // chunks: the full ones plus one open chunk per wave of the grid and sub-bucket
-  const int64_t cmax = (int64_t)div_up((uint64_t)rows, (uint64_t)PART_CH) + (int64_t)sgrid * (sblock / 64) * SB + 1;
-  QE_TRY(grow_buffer(&h->part_rec, &h->part_rec_bytes, (size_t)cmax * PART_CH * rb, ctx, "spill records"));
-  // chunk table: meta (count, then bucket << 32 | fill per chunk), the chunk ids grouped by
-  // sub-bucket, and (SB > 1) the planning counters: records (8 B), chunks, cursor, base per sub-bucket
-  const size_t tbl = ((size_t)(1 + cmax) * 8 + (size_t)cmax * 4 + 7) & ~(size_t)7;
-  QE_TRY(grow_buffer(&h->part_cnt, &h->part_cnt_bytes, tbl + (size_t)SB * 20, ctx, "chunk table"));
-  qi64* meta = (qi64*)h->part_cnt;
-  qi32* sorted = (qi32*)(meta + 1 + cmax);
-  unsigned long long* prec = (unsigned long long*)((uint8_t*)h->part_cnt + tbl);
-  qu32* pcnt = (qu32*)(prec + SB);
-  qu32* pcur = pcnt + SB;
-  qu32* pbase = pcur + SB;
-  const int64_t tmax = ctx->num_cus;  // aggregation slices of the spilled share (+ one per sub-bucket)
-  QE_TRY(grow_buffer(&h->part_slc, &h->part_slc_bytes, (size_t)(2 + 2 * (tmax + SB)) * 8, ctx, "spill slices"));
-  QE_TRY(ensure_defer(h, cmax * PART_CH));  // the aggregation pass's retry bitmaps index record slots
+  const int64_t kept_slots = P.lds_compact ? (int64_t)P.lds_compact : ((int64_t)1 << P.lds_log2);
+  const SpillGeometry G = spill_geometry(rows, ctx->num_cus, bpc, sblock, SB, rb, kept_slots, h->expected_groups, K);
+  QE_TRY(grow_buffer(&h->part_rec, &h->part_rec_bytes, G.rec_bytes, ctx, "spill records"));
+  QE_TRY(grow_buffer(&h->part_cnt, &h->part_cnt_bytes, G.table.bytes, ctx, "chunk table"));
+  const ChunkPtrs C = chunk_ptrs(h, G.table);
+  QE_TRY(grow_buffer(&h->part_slc, &h->part_slc_bytes, G.slice_bytes, ctx, "spill slices"));
+  QE_TRY(ensure_defer(h, G.rec_slots));  // the aggregation pass's retry bitmaps index record slots
   *used = true;
-  h->chunk_cap = cmax;
-  QE_HIP(hipMemsetAsync(meta, 0, 8, ctx->stream));
+  h->chunk_cap = G.cmax;
+  QE_HIP(hipMemsetAsync(C.meta, 0, 8, ctx->stream));
   if (L.narrow) QE_HIP(hipMemsetAsync(h->ctl + 7, 0, 8, ctx->stream));
-  // kept share: as many groups as one LDS table holds at a 6/8 load, the rest spilled (4096
-  // expected groups of the C4 shape: 75 % kept, half the records of an even split; 1B rows, 4096 /
-  // 5000 groups: 5/8 7.27 / 8.12 ms, 6/8 6.56 / 7.85, 7/8 6.62 / 10.79). The compact kept table
-  // too since round 6's record-major spill (7,000 groups, 1B rows, spilling pass + aggregation
-  // pass: 4/8 5.30 + 3.08 ms, 5/8 5.09 + 1.05, 6/8 4.94 + 0.61, 7/8 5.95 + 0.40)
-  const int load8 = spill_load8();
-  const int64_t kept_cap = P.lds_compact ? (int64_t)P.lds_compact : ((int64_t)1 << P.lds_log2);  // kept table's slots
-  const double keep = std::min(1.0, (double)(kept_cap * load8 / 8) / (double)std::max<int64_t>(1, h->expected_groups));
-  P.mp_keep = (qu64)(keep * 4294967296.0);
+  P.mp_keep = (qu64)G.mp_keep;
   P.part_rec = h->part_rec;
-  P.part_chunk = meta;
+  P.part_chunk = C.meta;
   int out_i = 0;
-  const uint32_t* defer_in = nullptr;
   // retry passes re-run the spill kernel over deferred rows only: those are bucket-0 rows, so
   // nothing is spilled twice
   bool misfit = false;
-  for (int pass = 0;; ++pass) {
-    QE_TRY(launch_pass(h, P, lds, fs, sgrid, pass, 0, out_i, defer_in, sblock));
-    bool done = false;
-    QE_TRY(settle_pass(h, P, &out_i, &defer_in, &done));
-    misfit = misfit || h->narrow_failed;
-    if (done) break;
-  }
+  QE_TRY(run_passes(h, P, lds, fs, G.sgrid, 0, &out_i, sblock, &misfit));
   if (misfit) {
     // a spilled value did not fit the 32-bit records: the kept rows are aggregated, the records
     // are not usable. The spilled rows (key hash >= mp_keep) go through one more fused pass over
@@ -2536,49 +2374,95 @@ static int spill_update(qe_hashagg* h, Plan& P, size_t lds, int64_t rows, bool* 
     R.mp_pass = -1;
     h->defer_dirty[0] = h->defer_dirty[1] = true;
     out_i = 0;
-    defer_in = nullptr;
-    for (int pass = 0;; ++pass) {
-      QE_TRY(launch_pass(h, R, lds, nullptr, 0, pass, 1, out_i, defer_in));
-      bool done = false;
-      QE_TRY(settle_pass(h, R, &out_i, &defer_in, &done));
-      if (done) break;
-    }
+    QE_TRY(run_passes(h, R, lds, nullptr, 0, 1, &out_i));
     h->jit_note = "multi-pass: 2 buckets, bucket 1 spilled, then re-read (a value outside the 32-bit records)";
     return QE_OK;
   }
   if (SB == 1) {
-    hipLaunchKernelGGL(k_spill_plan, dim3((unsigned)div_up((uint64_t)cmax, 256)), dim3(256), 0, ctx->stream,
-                       (const qi64*)meta, (qi64)tmax, (qi64*)h->part_slc, sorted);
+    hipLaunchKernelGGL(k_spill_plan, dim3((unsigned)div_up((uint64_t)G.cmax, 256)), dim3(256), 0, ctx->stream,
+                       (const qi64*)C.meta, (qi64)G.tmax, (qi64*)h->part_slc, C.sorted);
     QE_TRY(launch_check("k_spill_plan"));
   } else {  // chunks grouped by sub-bucket and sliced, as after the radix scatter
-    QE_HIP(hipMemsetAsync(prec, 0, (size_t)SB * 20, ctx->stream));
-    const unsigned pg = (unsigned)div_up((uint64_t)cmax, CHUNK_PER_WG);
-    hipLaunchKernelGGL(k_chunk_hist, dim3(pg), dim3(256), 0, ctx->stream, (const qi64*)meta, (qi32)SB, pcnt, prec);
-    QE_TRY(launch_check("k_chunk_hist"));
-    hipLaunchKernelGGL(k_chunk_slices, dim3(1), dim3(1024), 0, ctx->stream, (const qi64*)meta, (qi32)SB, (qi64)tmax,
-                       (const qu32*)pcnt, (const unsigned long long*)prec, (qi64*)h->part_slc, pbase);
-    QE_TRY(launch_check("k_chunk_slices"));
-    hipLaunchKernelGGL(k_chunk_place, dim3(pg), dim3(256), 0, ctx->stream, (const qi64*)meta, (qi32)SB,
-                       (const qu32*)pbase, pcur, sorted);
-    QE_TRY(launch_check("k_chunk_place"));
+    QE_HIP(hipMemsetAsync(C.prec, 0, (size_t)SB * 20, ctx->stream));
+    QE_TRY(plan_chunks(h, C, G.cmax, SB, G.tmax));
   }
-  Q.n = cmax * PART_CH;  // record slots (the retry bitmaps index them)
+  Q.n = G.rec_slots;  // record slots (the retry bitmaps index them)
   Q.part_rec = h->part_rec;
-  Q.part_chunk = meta;
-  Q.part_sorted = sorted;
+  Q.part_chunk = C.meta;
+  Q.part_sorted = C.sorted;
   Q.part_slice = (qi64*)h->part_slc;
   Q.ovf = h->ovf;
   Q.ovf_cap = h->ovf_cap;
-  defer_in = nullptr;
-  for (int pass = 0;; ++pass) {
-    QE_TRY(launch_pass(h, Q, lds, fa, (int)(tmax + SB), pass, 1, out_i, defer_in));
-    bool done = false;
-    QE_TRY(settle_pass(h, Q, &out_i, &defer_in, &done));
-    if (done) break;
-  }
+  QE_TRY(run_passes(h, Q, lds, fa, (int)(G.tmax + SB), 1, &out_i));
   h->jit_note = std::string("multi-pass: 2 buckets") + (P.lds_compact ? " (compact kept table)" : "") +
                 ", bucket 1 spilled" + (SB > 1 ? " in " + std::to_string(SB) + " sub-buckets" : std::string()) + " as " +
-                std::to_string(rb) + " B records (" + (L.colmode ? "column" : "value") + (L.narrow ? " words, 32-bit)" : " words)");
+                std::to_string(rb) + " B records (" + record_words_note(L);
+  return QE_OK;
+}
+
+// One rung of the ladder (qe_agg_paths.hpp agg_ladder). *taken: the update goes on with P, *lds and
+// *mp_n as the rung set them; *finished: the rung ran the whole update. Neither: its source
+// generation or compile failed, or its spilling pass declined, and the next rung is tried.
+static int try_rung(qe_hashagg* h, Plan& P, const AggCandidate& c, int64_t rows, const AggKnobs& K, size_t* lds,
+                    int* mp_n, bool* taken, bool* finished) {
+  qe_ctx* ctx = h->ctx;
+  if (c.path == PATH_REGULAR || c.path == PATH_PARTITION || c.path == PATH_GLOBAL) {
+    *taken = true;  // nothing to set up here (the radix partition: run_update's tail)
+    return QE_OK;
+  }
+  std::string src;
+  size_t jl = 0;
+  Plan T = P;
+  bool spill = false;
+  switch (c.path) {
+    case PATH_COMPACT:
+    case PATH_COMPACT_SPILL:
+    case PATH_COMPACT_TWOPASS: {
+      T.lds_log2 = 16;  // (unused by the compact kernel; keeps adapt_after_update from resizing)
+      T.lds_compact = c.compact_slots;
+      if (c.mp_n) {
+        T.mp_n = c.mp_n;
+        T.mp_pass = 0;
+      }
+      spill = c.path == PATH_COMPACT_SPILL;
+      hipFunction_t f = nullptr;
+      int bpc = 0;
+      if (!gen_fused_source(T, T.lds_log2, &src, &jl, spill)) return QE_OK;
+      if (!spill && jit_kernel(ctx, src, &f, &bpc, "qe_fused", fused_block(16)) != QE_OK) return QE_OK;
+      QE_TRY(ensure_overflow(h, c.ovf_records));
+      QE_HIP(hipMemsetAsync(h->ctl + 7, 0, 8, ctx->stream));  // the compact table's fit flag
+      break;
+    }
+    case PATH_SPILL:
+    case PATH_KEYHASH: {
+      T.mp_n = c.mp_n;
+      T.mp_pass = 0;
+      const size_t lds_mp = lds_layout_at(h, &T, c.tlog2);
+      if (ctx->jit && !gen_fused_source(T, T.lds_log2, &src, &jl)) return QE_OK;
+      jl = lds_mp;
+      QE_TRY(ensure_overflow(h, c.ovf_records));
+      spill = c.path == PATH_SPILL;
+      break;
+    }
+  }
+  T.ovf = h->ovf;
+  T.ovf_cap = h->ovf_cap;
+  if (c.path != PATH_COMPACT_SPILL) {  // (a kept compact table's plan goes on only with its spill)
+    P = T;
+    *lds = jl;
+    *mp_n = c.mp_n;
+    *taken = !spill;
+  }
+  if (spill) {
+    Plan& X = c.path == PATH_SPILL ? P : T;
+    QE_TRY(spill_update(h, X, jl, rows, K, finished));
+    if (*finished) {
+      h->row_base += rows;
+      adapt_after_update(h, jl, X.lds_log2);
+    } else if (c.path == PATH_SPILL) {
+      *taken = true;  // two fused passes, as set up here (PATH_KEYHASH's set-up)
+    }
+  }
   return QE_OK;
 }
 
@@ -2597,229 +2481,38 @@ static int run_update(qe_hashagg* h, Plan& P) {
   h->last_kernel_ms = 0.0;
   h->last_launches = 0;
   h->chunk_cap = 0;
-  // groups beyond the LDS table: radix-partition the selected rows by key hash first, then
-  // aggregate record slices in LDS (events bracket the whole sequence)
   hipFunction_t pfn = nullptr;
   int pgrid = 0;
-  QE_HIP(hipEventRecord(h->ev[0], ctx->stream));
-  // Groups just beyond one LDS table: 2 passes of the fused kernel, each keeping one bucket of
-  // key hashes, read the columns twice but write and re-read no records. Measured at 200M rows
-  // (C4 shape): 2048 groups 1.86 ms in 2 passes against ~3.1 ms radix-partitioned; 3 passes lose
-  // their edge (3000 groups 2.88 ms, 3800 groups 3.44 ms against 3.09 ms partitioned).
-  size_t lds_mp = 0;
-  int mp_n = 0;
-  // Groups just past the regular LDS table: one pass with the compact table (qe_jit.hip
-  // compact_*, 32-bit keys, <= 92 % load) when the plan shape and the expected groups allow it
-  // (QE_LDS_COMPACT=0: never; read per call), before key-hash passes / spilling.
-  const char* ce = getenv("QE_LDS_COMPACT");
-  if (!lds && ctx->jit && h->expected_groups > 0 && !h->compact_off && !(ce && ce[0] == '0') && compact_ok(P)) {
-    Plan T = P;
-    T.lds_log2 = 16;  // (unused by the compact kernel; keeps adapt_after_update from resizing)
-    const size_t bps = compact_slot_bytes(T);
-    const int64_t nsl = ((int64_t)((lds_budget(ctx) - 512) / bps) - 66) & ~(int64_t)63;  // (+2 special, 64 sinks)
-    // expected groups at most QE_COMPACT_LOAD percent of the slots (default 98; 1B rows, one box,
-    // 6336 slots: 5,900 / 6,000 / 6,150 / 6,250 groups 4.04 / 4.02–4.15 / 4.24 / 4.97 ms in one pass
-    // at 93–99 %, against 5.45–5.71 ms for the spilling pass; round 5: 5,400 / 5,700 groups 3.76 /
-    // 3.87 ms at 88–92 %)
-    static const int cload = [] {
-      const char* e = getenv("QE_COMPACT_LOAD");
-      const int v = e && *e ? atoi(e) : 98;
-      return v >= 50 && v <= 99 ? v : 98;
-    }();
-    if (nsl >= 512 && nsl * cload >= h->expected_groups * 100) {
-      T.lds_compact = (qi32)nsl;
-      std::string src;
-      size_t jl = 0;
-      hipFunction_t f = nullptr;
-      int bpc = 0;
-      if (gen_fused_source(T, T.lds_log2, &src, &jl) && jit_kernel(ctx, src, &f, &bpc, "qe_fused", fused_block(16)) == QE_OK) {
-        const uint64_t need = (uint64_t)ctx->num_cus * 8 * ((uint64_t)nsl + 2);
-        if (h->ovf_cap < need) {
-          dev_free(ctx, h->ovf);
-          h->ovf = nullptr;
-          h->ovf_cap = 0;
-          QE_TRY(dev_alloc(ctx, need * h->rec_bytes, (void**)&h->ovf));
-          h->ovf_cap = need;
-        }
-        T.ovf = h->ovf;
-        T.ovf_cap = h->ovf_cap;
-        QE_HIP(hipMemsetAsync(h->ctl + 7, 0, 8, ctx->stream));
-        P = T;
-        lds = jl;
-      }
-    }
+  QE_HIP(hipEventRecord(h->ev[0], ctx->stream));  // (the events bracket the whole sequence)
+  // the path: the first rung of the ladder that works out (qe_agg_paths.hpp)
+  const AggKnobs K = lds ? agg_knobs() : agg_knobs_now();  // (the one-pass table reads no knob per call)
+  AggLadderIn in;
+  in.jit = ctx->jit != 0;
+  in.num_cus = ctx->num_cus;
+  in.expected_groups = h->expected_groups;
+  in.compact_off = h->compact_off;
+  in.regular_bytes = lds;
+  Plan S;  // scratch for table sizes
+  if (!lds) {
+    S = P;
+    in.compact_ok = in.jit && compact_ok(P);
+    in.compact_slot_bytes = in.compact_ok ? compact_slot_bytes(P) : 0;
+    in.fused_budget = lds_budget(ctx);
+    in.pagg_budget = pagg_lds_budget(pagg_block());
   }
-  // Past the compact table (~5K groups for C4) and up to ~1.5 tables' worth: ONE spilling pass
-  // whose kept share (key hashes below mp_keep, 6/8 of the compact table's slots) stays in the
-  // compact table and whose other rows are written as records for one aggregation pass
-  // (spill_update), instead of the 8-bucket partitioned path (QE_COMPACT_SPILL=0: off).
-  if (!lds && ctx->jit && h->expected_groups > 0 && !h->compact_off && !(ce && ce[0] == '0') && compact_ok(P)) {
-    static const bool cs_env = [] {
-      const char* e = getenv("QE_COMPACT_SPILL");
-      return !(e && e[0] == '0');
-    }();
-    Plan T = P;
-    T.lds_log2 = 16;
-    const size_t bps = compact_slot_bytes(T);
-    const int64_t nsl = ((int64_t)((lds_budget(ctx) - 512 - 256) / bps) - 66) & ~(int64_t)63;  // (+ spill chunk state)
-    // the spilled share goes through the regular aggregation table: at most half of it (1B rows:
-    // 5,500 / 6,500 groups 5.95 / 6.59 ms against 8.23 / 8.25 partitioned; 8,192 groups, whose
-    // ~3.4K spilled groups fill 84 % of a 4096-slot table, 11.0 against 8.1 ms)
-    int tl = 16;
-    {
-      Plan Q = T;
-      Q.lds_compact = 0;
-      Q.mp_n = 0;
-      const size_t pbudget = pagg_block() == 1024 ? (size_t)152 * 1024 : HA_LDS_BUDGET;
-      while (tl >= 8 && lds_layout_at(h, &Q, tl) > pbudget) --tl;
-    }
-    // QE_SPILL_MAXPCT (default 70): the spilled groups (expected groups beyond the kept share)
-    // may fill this percentage of each sub-bucket's aggregation table; 0 = round 4's rule (kept
-    // share counted at 3/4, half the table). 1B rows, one box, C4 shape, record-major spill at a
-    // 6/8 kept share: 7,500 groups 5.97 ms, 8,192 groups in one spilled bucket (84 % of its table)
-    // 6.82 ms, against 7.63 ms partitioned at 8,192; two sub-buckets reach ~10.5K groups (11,500
-    // groups at 85 %: 8.63 ms, past the partitioned update's ~8.0). Round 5 (chunk-columnar spill
-    // at 7/8): 7.04 ms at 7,000 groups, 8.71 at 8,192, so 60 % stopped at ~7.9K groups
-    static const int sp_pct = [] {
-      const char* e = getenv("QE_SPILL_MAXPCT");
-      const int v = e && *e ? atoi(e) : 70;
-      return v >= 10 && v <= 90 ? v : 0;
-    }();
-    // the spilled share in SB sub-buckets (spill_hash's low bits), each aggregated by its own
-    // slices: the fewest (1 or 2) whose aggregation tables stay within that percentage
-    // (QE_SPILL_SUBBUCKETS: the most, 1, 2 or 4). 1B rows, one box: 8,192 groups 7.19 ms with
-    // one spilled bucket, 7.07 with two (at 7,000 groups one: 6.24 against 6.55); 9,000 / 10,000
-    // groups in two 7.28 / 7.66 ms, 12,000 / 16,000 in four 8.57 / 9.53, against 8.0–8.2 ms
-    // partitioned on that box
-    static const int sb_max = [] {
-      const char* e = getenv("QE_SPILL_SUBBUCKETS");
-      const int v = e && *e ? atoi(e) : 2;
-      return v == 1 || v == 2 || v == 4 ? v : 2;
-    }();
-    const int64_t kept_share = nsl * spill_load8() / 8, per_sb = ((int64_t)1 << tl) * sp_pct / 100;
-    int sb = 1;
-    while (sp_pct && sb < sb_max && h->expected_groups - kept_share > sb * per_sb) sb *= 2;
-    const int64_t spill_max = sp_pct ? kept_share + sb * per_sb : nsl * 3 / 4 + ((int64_t)1 << tl) / 2;
-    if (cs_env && nsl >= 512 && tl >= 8 && h->expected_groups <= spill_max) {
-      T.lds_compact = (qi32)nsl;
-      T.mp_n = 1 + sb;
-      T.mp_pass = 0;
-      std::string src;
-      size_t jl = 0;
-      if (gen_fused_source(T, T.lds_log2, &src, &jl, true)) {
-        const uint64_t need = (uint64_t)ctx->num_cus * 8 * ((uint64_t)nsl + 2);
-        if (h->ovf_cap < need) {
-          dev_free(ctx, h->ovf);
-          h->ovf = nullptr;
-          h->ovf_cap = 0;
-          QE_TRY(dev_alloc(ctx, need * h->rec_bytes, (void**)&h->ovf));
-          h->ovf_cap = need;
-        }
-        T.ovf = h->ovf;
-        T.ovf_cap = h->ovf_cap;
-        QE_HIP(hipMemsetAsync(h->ctl + 7, 0, 8, ctx->stream));
-        bool used = false;
-        QE_TRY(spill_update(h, T, jl, rows, &used));
-        if (used) {
-          h->row_base += rows;
-          adapt_after_update(h, jl, T.lds_log2);
-          return QE_OK;
-        }
-      }
-    }
+  const AggLadder ladder = agg_ladder(in, K, [&](int log2) { return lds_layout_at(h, &S, log2); });
+  int mp_n = 0, rung = 0;
+  for (bool taken = false; !taken; ++rung) {
+    bool finished = false;
+    QE_TRY(try_rung(h, P, ladder.c[rung], rows, K, &lds, &mp_n, &taken, &finished));
+    if (finished) return QE_OK;
   }
-  // Beyond the compact spill (~6.75K–10K groups for C4): two key-hash passes over the columns,
-  // each keeping half the groups in the compact table (QE_COMPACT_TWOPASS=1, opt-in: 1B rows, one
-  // box, 7,000 / 8,192 / 9,500 groups 8.02 / 8.17 / 9.09 ms against 7.78 / 7.81 / 7.96 ms for the
-  // partitioned update — each pass's fuller compact table costs ~4 ms).
-  bool no_spill = false;
-  if (!lds && ctx->jit && h->expected_groups > 0 && !h->compact_off && !(ce && ce[0] == '0') && compact_ok(P)) {
-    static const bool c2_env = [] {
-      const char* e = getenv("QE_COMPACT_TWOPASS");
-      return e && e[0] == '1';
-    }();
-    Plan T = P;
-    T.lds_log2 = 16;
-    const size_t bps = compact_slot_bytes(T);
-    const int64_t nsl = ((int64_t)((lds_budget(ctx) - 512) / bps) - 66) & ~(int64_t)63;
-    if (c2_env && nsl >= 512 && h->expected_groups <= nsl * 8 / 5) {
-      T.lds_compact = (qi32)nsl;
-      T.mp_n = 2;
-      T.mp_pass = 0;
-      std::string src;
-      size_t jl = 0;
-      hipFunction_t f = nullptr;
-      int bpc = 0;
-      if (gen_fused_source(T, T.lds_log2, &src, &jl) && jit_kernel(ctx, src, &f, &bpc, "qe_fused", fused_block(16)) == QE_OK) {
-        const uint64_t need = (uint64_t)ctx->num_cus * 8 * ((uint64_t)nsl + 2);
-        if (h->ovf_cap < need) {
-          dev_free(ctx, h->ovf);
-          h->ovf = nullptr;
-          h->ovf_cap = 0;
-          QE_TRY(dev_alloc(ctx, need * h->rec_bytes, (void**)&h->ovf));
-          h->ovf_cap = need;
-        }
-        T.ovf = h->ovf;
-        T.ovf_cap = h->ovf_cap;
-        QE_HIP(hipMemsetAsync(h->ctl + 7, 0, 8, ctx->stream));
-        P = T;
-        lds = jl;
-        mp_n = 2;
-        no_spill = true;
-      }
-    }
-  }
-  // The generic kernel (JIT off, or no specialised kernel) passes too, with its own 80 KiB budget:
-  // it has no partitioned path to fall back on, and global-only rows cost a device atomic each.
-  if (!lds && h->expected_groups > 0) {
-    int tlog2 = 16;
-    Plan T = P;
-    const size_t mbudget = ctx->jit ? lds_budget(ctx) : HA_LDS_BUDGET;
-    while (tlog2 >= 8 && lds_layout_at(h, &T, tlog2) > mbudget) --tlog2;
-    const int64_t per_pass = (((int64_t)1 << tlog2) * 5) / 8;
-    const int64_t np = tlog2 >= 8 ? (h->expected_groups + per_pass - 1) / per_pass : 0;
-    static const int64_t mp_max = [] {  // QE_MP_MAX: most bucket passes before partitioning
-      const char* e = getenv("QE_MP_MAX");
-      return (int64_t)(e && *e ? std::max(2, std::min(8, atoi(e))) : 2);
-    }();
-    if (np >= 2 && np <= (ctx->jit ? mp_max : 8)) {
-      T.mp_n = (qi32)np;
-      T.mp_pass = 0;
-      lds_mp = lds_layout_at(h, &T, tlog2);
-      std::string src;
-      size_t jl = 0;
-      // overflow records: a workgroup flushes at most its table's slots
-      const uint64_t need = (uint64_t)ctx->num_cus * 8 * (((uint64_t)1 << tlog2) + 2);
-      if (lds_mp && (!ctx->jit || gen_fused_source(T, T.lds_log2, &src, &jl))) {
-        if (h->ovf_cap < need) {
-          dev_free(ctx, h->ovf);
-          h->ovf = nullptr;
-          h->ovf_cap = 0;
-          QE_TRY(dev_alloc(ctx, need * h->rec_bytes, (void**)&h->ovf));
-          h->ovf_cap = need;
-        }
-        mp_n = (int)np;
-        T.ovf = h->ovf;
-        T.ovf_cap = h->ovf_cap;
-        P = T;
-        lds = lds_mp;
-      }
-    }
-  }
-  if (mp_n == 2 && ctx->jit && !no_spill) {
-    bool used = false;
-    QE_TRY(spill_update(h, P, lds, rows, &used));
-    if (used) {
-      h->row_base += rows;
-      adapt_after_update(h, lds, P.lds_log2);
-      return QE_OK;
-    }
-  }
+  const AggCandidate& path = ladder.c[rung - 1];
   const Plan P_rows = P;  // the batch's plan, for a partitioned update repeated with 64-bit records
   for (;;) {
-  if (!lds && mp_n == 0 && ctx->jit && h->expected_groups > 0) {
+  if (path.path == PATH_PARTITION) {
     Plan Q = P;
-    if (partition_rows(h, Q, &pfn, &pgrid) == QE_OK) {
+    if (partition_rows(h, Q, path.tlog2, K, &pfn, &pgrid) == QE_OK) {
       P = Q;
       if (P.n == 0) {
         QE_HIP(hipEventRecord(h->ev[1], ctx->stream));
@@ -2990,20 +2683,15 @@ int qe_hashagg_create_ex(qe_ctx* ctx, int32_t nkeys, const int32_t* key_types, i
   if (pinned_slot_alloc(&h->ctl_pin) != QE_OK) return bail(QE_ERR_OOM);
   if (dev_alloc(ctx, 64, (void**)&h->ctl) != QE_OK) return bail(fail(QE_ERR_OOM, "control allocation failed"));
   // (the control words are zeroed by the table's init launch below)
-  // LDS table: 2x the expected groups (load factor <= 0.5); a launch may shrink it down to
-  // 1.25x (lds_log2_min) to fit the per-workgroup budget, else the launch is global-only.
+  // LDS table range (qe_agg_paths.hpp lds_table_range)
   const int64_t eg = expected_groups > 0 ? expected_groups : 1024;
   h->expected_groups = eg;
   h->create_groups = eg;
-  int log2 = 8, log2_min = 8;
-  while (log2 < 16 && ((int64_t)1 << log2) < 2 * eg) ++log2;
-  while (log2_min < 16 && ((int64_t)1 << log2_min) < (5 * eg + 3) / 4) ++log2_min;
-  const size_t budget = lds_budget(ctx);
-  while (log2 > log2_min && lds_bytes_min(h, log2) > budget) --log2;
-  h->lds_log2 = lds_bytes_min(h, log2) <= budget ? log2 : 0;
-  h->lds_log2_min = log2_min;
+  const LdsRange lr = lds_table_range(eg, h->acc, naggs, !ctx->jit, lds_budget(ctx));
+  h->lds_log2 = lr.log2;
+  h->lds_log2_min = lr.log2_min;
   // workgroups per CU: as many as the smallest layout of the LDS table allows (max 8)
-  const int per_cu = h->lds_log2 ? std::max<int>(1, std::min<int>(8, (int)((160 * 1024) / lds_bytes_min(h, h->lds_log2)))) : 8;
+  const int per_cu = h->lds_log2 ? std::max<int>(1, std::min<int>(8, (int)((160 * 1024) / lds_bytes_min(h->acc, naggs, h->lds_log2, !ctx->jit)))) : 8;
   h->grid = ctx->num_cus * per_cu;
   // overflow records: at most one per LDS slot per workgroup
   if (h->lds_log2) {

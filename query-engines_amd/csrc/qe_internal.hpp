@@ -11,6 +11,7 @@
 
 #include "qe_hip.h"
 #include "qe_dev.hpp"
+#include "qe_agg_paths.hpp"
 
 struct qe_ctx {
   int device = 0;
@@ -80,9 +81,7 @@ int parallel_h2d_copy(qe_ctx* ctx, void* dst, const void* src, size_t n);
 int parallel_h2d_file(qe_ctx* ctx, void* dst, int fd, int64_t off, size_t n);
 // Per-plan kernel specialisation (qe_jit.hip).
 bool gen_fused_source(const qe::Plan& P, int log2, std::string* src, size_t* lds_bytes, bool spill = false);
-// Exact fp64 SUM in the specialised kernels' LDS tables: the 192-bit carry window through the per-wave
-// queue. LDS words per slot beyond acc.
-inline int fx_window_idx_words() { return 2; }
+// (fx_window_idx_words: qe_agg_paths.hpp)
 // compact fused LDS table (Plan.lds_compact): plan shapes it supports, bytes per slot, 32-bit MIN/MAX
 bool compact_ok(const qe::Plan& P);
 size_t compact_slot_bytes(const qe::Plan& P);
