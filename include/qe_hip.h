@@ -276,6 +276,52 @@ int qe_take(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int3
  * single-workgroup path takes. Tests read the boundaries from here. */
 int qe_sort_layout(int32_t* tile_rows, int32_t* small_max);
 
+/* ---- equi-JOIN (build-defined; the reference's SQL has no JOIN) ------------------------------
+ * A hash table is built once from the key column of one side (the build side) and probed by
+ * batches of the other. The result is (probe row, build row) index pairs that qe_take /
+ * qe_take_or_null materialise.
+ * Key: ONE column of type INT64, INT32, DATE32, UINT8, BOOL or FLOAT64, one 64-bit key word per
+ * row: integers sign-extended, UINT8 and BOOL zero-extended (an INT32 build key matches an INT64
+ * probe key of equal value); FLOAT64 by the group keys' Double.equals (every NaN one key,
+ * -0.0 != +0.0) and only against FLOAT64. Any other type or pairing: QE_ERR_INVALID_ARG. A null key
+ * matches nothing, on either side; null build rows are not inserted. UTF8 and composite keys reach
+ * these calls as dictionary codes (qe_strdict_encode / qe_strdict_encode_tuple).
+ * Table: open addressing with linear probing over `slots` slots, the least power of two >=
+ * max(64, 2 x non-null build rows); a key's home slot is fmix64(key word) & (slots - 1), fmix64 the
+ * murmur3 64-bit finaliser. Every 64-bit value is a legal key.
+ * Order: pairs come sorted by probe row and, within a probe row, by ascending build row: one
+ * sequence, bit-identical from run to run, whatever slot a key landed in. */
+#define QE_JOIN_INNER 0
+#define QE_JOIN_LEFT  1   /* probe-side outer: an unmatched probe row pairs with build index -1 */
+typedef struct qe_join qe_join;
+
+/* Builds the table over key->length <= 2^31-1 rows (zero rows or all nulls: a valid, empty table).
+ * Working memory and the table come from the library's allocator (QE_ERR_OOM when it fails). Reads
+ * back the non-null row count of a nullable key and the longest run of equal keys; only a build
+ * side with duplicate keys pays for ordering its runs. The key column is not needed afterwards. */
+int qe_join_build(qe_ctx* ctx, const qe_column* key, qe_join** out);
+int qe_join_destroy(qe_join* j);
+/* Pairs of the probe batch `key` (<= 2^31-1 rows). probe_idx / build_idx: INT32 without validity;
+ * their length on entry is the row capacity and is set on return. *pairs always receives the exact
+ * pair count; if the capacity is short nothing is written and the call returns QE_ERR_CAPACITY (call
+ * again with *pairs rows). A table whose keys are unique (qe_join_stats max_dup == 1) never needs
+ * more than key->length rows. More than 2^31-1 pairs: QE_ERR_UNSUPPORTED. QE_JOIN_LEFT emits
+ * exactly one pair (i, -1) for an unmatched or null-key probe row i. One read-back (the count). */
+int qe_join_probe(qe_join* j, const qe_column* key, int32_t kind,
+                  qe_column* probe_idx, qe_column* build_idx, int64_t* pairs);
+/* Semi / anti join: mask[i] = (probe row i has a match) XOR anti, so a null probe key is kept by
+ * anti. `mask`: BOOL without validity, capacity >= key->length rows, whole 32-bit words written.
+ * Stream-ordered, no host wait: a filter queues right behind it. */
+int qe_join_probe_mask(qe_join* j, const qe_column* key, int32_t anti, qe_column* mask);
+/* Measurement hook: the non-null build rows, the distinct keys, the longest run of equal keys and
+ * the slot count. Synchronises. */
+int qe_join_stats(qe_join* j, int64_t* build_rows, int64_t* distinct, int64_t* max_dup, int64_t* slots);
+/* qe_take where index -1 means "no row": that output row is null (zero where a value is written)
+ * and no error. Every output must have a validity buffer (QE_ERR_INVALID_ARG otherwise). Any other
+ * index outside [0, inputs.length) behaves as in qe_take. */
+int qe_take_or_null(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int32_t ncols,
+                    qe_column* outs, const int64_t* utf8_capacity);
+
 /* ---- aggregates ------------------------------------------------------------------------- */
 #define QE_AGG_SUM 1
 #define QE_AGG_MIN 2

@@ -201,6 +201,11 @@ int64_t utf8_gather_tiles(int64_t rows);
 int utf8_gather_lengths(qe_ctx* ctx, const int2* sl, int64_t rows, int64_t* tsum);
 int utf8_gather_copy(qe_ctx* ctx, const int2* sl, int64_t rows, const int64_t* tsum, const uint8_t* src,
                      int32_t* out_offs, uint8_t* out_values);
+// The radix sort's multi-workgroup passes over caller buffers (qe_sort.hip): a stable sort of n
+// (word, index) pairs by the low `bits` bits of the words, starting in buffer 0 of each kind; *cur =
+// the buffer holding the sorted indices. `scratch`: sort_pairs_scratch_bytes(n) bytes.
+size_t sort_pairs_scratch_bytes(int64_t n);
+int sort_pairs(qe_ctx* ctx, uint64_t* const words[2], int32_t* const idx[2], int64_t n, int bits, void* scratch, int* cur);
 
 // ---- type helpers ---------------------------------------------------------------------------
 inline int type_width(int32_t t) {

@@ -18,6 +18,10 @@
 // qe_take
 //   k_take: one row per lane, validity / BOOL words built per wave with __ballot; UTF8 through the
 //   (start, length) pairs, length scan and byte copy of qe_filter.hip.
+// qe_take_or_null
+//   k_take<true>: index -1 is "no row" and gives a null row (the build side of a LEFT join).
+// sort_pairs
+//   the count / scan / scatter passes over a caller's (word, index) buffers (qe_join.hip).
 #include "qe_internal.hpp"
 #include "qe_sort_key.hpp"
 
@@ -388,7 +392,9 @@ __device__ __forceinline__ void store_bits64(uint32_t* __restrict__ bm, int64_t 
 }
 
 // Output row i = input row idx[i], one row per lane. An index outside [0, nin) reads nothing: the
-// row gets a zero value and a null bit, and *flag is set.
+// row gets a zero value and a null bit, and *flag is set. OR_NULL (qe_take_or_null): index -1 means
+// "no row" and is written the same way without setting the flag.
+template <bool OR_NULL>
 __global__ void __launch_bounds__(256) k_take(const int32_t* __restrict__ idx, int64_t m, int64_t nin, TakeArgs A,
                                               unsigned* __restrict__ flag) {
   const int lane = threadIdx.x & 63;
@@ -400,7 +406,7 @@ __global__ void __launch_bounds__(256) k_take(const int32_t* __restrict__ idx, i
     const bool live = i < m;
     const int64_t r = live ? (int64_t)idx[i] : 0;
     const bool ok = live && (uint64_t)r < (uint64_t)nin;
-    if (live && !ok) *flag = 1u;
+    if (live && !ok && !(OR_NULL && r == -1)) *flag = 1u;
     for (int k = 0; k < A.ncols; ++k) {
       const TakeCol& C = A.cols[k];
       if (C.width == 8) {
@@ -439,6 +445,36 @@ struct DevBlock {  // working memory of one call: freed stream-ordered when the 
 };
 
 inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
+
+// The multi-workgroup passes for other translation units (qe_join.hip orders build rows by slot):
+// a stable sort of n (word, index) pairs by the low `bits` bits of the words, between the two
+// buffers of each kind, starting in buffer 0. *cur = the buffer that holds the sorted indices (the
+// words of the last pass are not written). `scratch`: sort_pairs_scratch_bytes(n) bytes.
+size_t sort_pairs_scratch_bytes(int64_t n) {
+  const int64_t ntiles = (int64_t)div_up((uint64_t)std::max<int64_t>(n, 1), SORT_TILE);
+  return 2 * align256((size_t)(256 * ntiles + 1) * 8);
+}
+
+int sort_pairs(qe_ctx* ctx, uint64_t* const words[2], int32_t* const idx[2], int64_t n, int bits, void* scratch, int* cur) {
+  *cur = 0;
+  if (n <= 0) return QE_OK;
+  const int64_t ntiles = (int64_t)div_up((uint64_t)n, SORT_TILE);
+  int64_t* d_counts = (int64_t*)scratch;
+  int64_t* d_offs = (int64_t*)((char*)scratch + sort_pairs_scratch_bytes(n) / 2);
+  const int nd = (bits + 7) / 8;
+  for (int j = 0; j < nd; ++j) {
+    const int shift = 8 * j, c = *cur;
+    hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, words[c], n, shift, ntiles,
+                       d_counts);
+    QE_TRY(launch_check("k_sort_count"));
+    QE_TRY(exclusive_scan_i64(ctx, d_counts, d_offs, 256 * ntiles));
+    hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, words[c], idx[c],
+                       j + 1 < nd ? words[c ^ 1] : (uint64_t*)nullptr, idx[c ^ 1], n, shift, ntiles, d_offs);
+    QE_TRY(launch_check("k_sort_scatter"));
+    *cur = c ^ 1;
+  }
+  return QE_OK;
+}
 
 }  // namespace qe
 
@@ -606,8 +642,11 @@ int qe_sort_indices(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, in
   return QE_OK;
 }
 
-int qe_take(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int32_t ncols, qe_column* outs,
-            const int64_t* utf8_capacity) {
+}  // extern "C"
+
+// qe_take, and qe_take_or_null (or_null: index -1 is "no row", and every output needs a validity buffer).
+static int take_impl(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int32_t ncols, qe_column* outs,
+                     const int64_t* utf8_capacity, bool or_null) {
   QE_TRY(ctx_enter(ctx));
   QE_CHECK(indices != nullptr, QE_ERR_INVALID_ARG, "take: null indices");
   QE_CHECK(indices->type == QE_TYPE_INT32 && !indices->validity, QE_ERR_INVALID_ARG,
@@ -633,6 +672,7 @@ int qe_take(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int3
              (long long)m);
     QE_CHECK((!in.validity || out.validity) && ((uintptr_t)out.validity & 3) == 0, QE_ERR_INVALID_ARG,
              "take: output %d needs a 4-byte aligned validity buffer", i);
+    QE_CHECK(!or_null || out.validity, QE_ERR_INVALID_ARG, "take: output %d needs a validity buffer (index -1 gives a null row)", i);
     QE_CHECK(!boolean || ((uintptr_t)out.values & 3) == 0, QE_ERR_INVALID_ARG, "take: BOOL output %d must be 4-byte aligned", i);
     QE_CHECK(!utf8 || ((in.offsets || nin == 0) && out.offsets), QE_ERR_INVALID_ARG, "take: UTF8 column %d needs offsets", i);
     QE_CHECK(!utf8 || (utf8_capacity && utf8_capacity[i] >= 0), QE_ERR_INVALID_ARG,
@@ -668,7 +708,12 @@ int qe_take(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int3
   }
   if (ncols > 0) {
     const int grid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)m, 256), (int64_t)ctx->num_cus * 8);
-    hipLaunchKernelGGL(k_take, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t*)indices->values, m, nin, args, d_flag);
+    if (or_null)
+      hipLaunchKernelGGL(k_take<true>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t*)indices->values, m, nin, args,
+                         d_flag);
+    else
+      hipLaunchKernelGGL(k_take<false>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t*)indices->values, m, nin, args,
+                         d_flag);
     QE_TRY(launch_check("k_take"));
   }
   // the flag and the UTF8 byte totals come back together, before any byte is copied
@@ -697,6 +742,18 @@ int qe_take(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int3
                               (uint8_t*)outs[i].values));
   for (int i = 0; i < ncols; ++i) outs[i].length = m;
   return QE_OK;
+}
+
+extern "C" {
+
+int qe_take(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int32_t ncols, qe_column* outs,
+            const int64_t* utf8_capacity) {
+  return take_impl(ctx, indices, inputs, ncols, outs, utf8_capacity, false);
+}
+
+int qe_take_or_null(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int32_t ncols, qe_column* outs,
+                    const int64_t* utf8_capacity) {
+  return take_impl(ctx, indices, inputs, ncols, outs, utf8_capacity, true);
 }
 
 }  // extern "C"

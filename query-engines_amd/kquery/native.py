@@ -47,6 +47,7 @@ OP_AND, OP_OR, OP_NOT, OP_IS_NULL, OP_IS_NOT_NULL = 20, 21, 22, 23, 24
 AGG_SUM, AGG_MIN, AGG_MAX, AGG_COUNT, AGG_COUNT_STAR, AGG_AVG = 1, 2, 3, 4, 5, 6
 
 SORT_DESC, SORT_NULLS_FIRST = 1, 2  # qe_sort_indices flag bits (0: ascending, nulls last)
+JOIN_INNER, JOIN_LEFT = 0, 1  # qe_join_probe kinds
 
 MAX_KEYS, MAX_AGGS, MAX_COLS, MAX_TERMS, MAX_TOKENS = 4, 8, 8, 8, 16
 TOK_COL, TOK_LIT, TOK_ADD, TOK_SUB, TOK_MUL, TOK_DIV = 1, 2, 3, 4, 5, 6
@@ -225,6 +226,12 @@ SIGNATURES = [
     ("qe_sort_indices", C.c_int, [_P, _COLP, C.POINTER(C.c_int32), C.c_int32, C.c_int64, _COLP]),
     ("qe_take", C.c_int, [_P, _COLP, _COLP, C.c_int32, _COLP, _I64P]),
     ("qe_sort_layout", C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("qe_join_build", C.c_int, [_P, _COLP, _PP]),
+    ("qe_join_destroy", C.c_int, [_P]),
+    ("qe_join_probe", C.c_int, [_P, _COLP, C.c_int32, _COLP, _COLP, _I64P]),
+    ("qe_join_probe_mask", C.c_int, [_P, _COLP, C.c_int32, _COLP]),
+    ("qe_join_stats", C.c_int, [_P, _I64P, _I64P, _I64P, _I64P]),
+    ("qe_take_or_null", C.c_int, [_P, _COLP, _COLP, C.c_int32, _COLP, _I64P]),
     ("qe_agg_global", C.c_int, [_P, _COLP, _COLP, C.POINTER(QeGlobalAgg)]),
     ("qe_agg_global_partial", C.c_int, [_P, _COLP, _COLP, C.c_int64, _P]),
     ("qe_agg_global_merge", C.c_int, [_P, C.c_int32, _P, C.c_int32, C.POINTER(QeGlobalAgg)]),

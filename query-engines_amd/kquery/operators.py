@@ -237,6 +237,17 @@ def take(indices: DeviceColumn, cols: Sequence[DeviceColumn],
     """qe_take: row indices[i] of every column, validity included. utf8_bytes[c]: the value bytes
     UTF8 output c needs (the sum of the taken lengths); None sizes it as the input's bytes, which
     is enough when no index repeats."""
+    return _take(indices, cols, utf8_bytes, False)
+
+
+def take_or_null(indices: DeviceColumn, cols: Sequence[DeviceColumn],
+                 utf8_bytes: Optional[Sequence[Optional[int]]] = None) -> List[DeviceColumn]:
+    """qe_take_or_null: as take, but index -1 means "no row" and gives a null row, so every output
+    is nullable (the build side of a LEFT join)."""
+    return _take(indices, cols, utf8_bytes, True)
+
+
+def _take(indices: DeviceColumn, cols: Sequence[DeviceColumn], utf8_bytes, or_null: bool) -> List[DeviceColumn]:
     import torch
 
     from .columnar import bitmap_bytes
@@ -246,26 +257,256 @@ def take(indices: DeviceColumn, cols: Sequence[DeviceColumn],
     dev = ctx.torch_device
     outs, caps = [], []
     for i, c in enumerate(cols):
+        nullable = c.nullable or or_null
         if c.type != N.TYPE_UTF8:
-            outs.append(DeviceColumn.empty(c.type, m, c.nullable, ctx=ctx))
+            outs.append(DeviceColumn.empty(c.type, m, nullable, ctx=ctx))
             caps.append(0)
             continue
         cap = utf8_bytes[i] if utf8_bytes is not None and utf8_bytes[i] is not None else None
         if cap is None:
             cap = int(c.offsets[c.length].item() - c.offsets[0].item()) if c.length else 0
         outs.append(DeviceColumn(N.TYPE_UTF8, m, torch.empty(max(cap, 1), dtype=torch.uint8, device=dev),
-                                 torch.zeros(max(bitmap_bytes(m), 4), dtype=torch.uint8, device=dev) if c.nullable else None,
+                                 torch.zeros(max(bitmap_bytes(m), 4), dtype=torch.uint8, device=dev) if nullable else None,
                                  torch.empty(m + 1, dtype=torch.int32, device=dev), ctx))
         outs[-1].max_len = c.max_len
         caps.append(cap)
     ic = indices.as_c()
+    fn = N.lib().qe_take_or_null if or_null else N.lib().qe_take
     for s in range(0, len(cols), N.MAX_COLS):  # qe_take gathers up to 8 columns per launch
         part = cols[s:s + N.MAX_COLS]
         ins = (N.QeColumn * len(part))(*[c.as_c() for c in part])
         os_ = (N.QeColumn * len(part))(*[o.as_c() for o in outs[s:s + N.MAX_COLS]])
         cp = (N.C.c_int64 * len(part))(*caps[s:s + N.MAX_COLS])
-        N.check(N.lib().qe_take(ctx.handle, N.C.byref(ic), ins, len(part), os_, cp))
+        N.check(fn(ctx.handle, N.C.byref(ic), ins, len(part), os_, cp))
     return outs
+
+
+# ---------------------------------------------------------------------------------------------------
+# Equi-join (build-defined): device hash build / probe -> row-index pairs
+# ---------------------------------------------------------------------------------------------------
+class JoinTable:
+    """The device hash table of one build side (qe_join_build); close() releases it."""
+
+    def __init__(self, ctx, handle):
+        self.ctx = ctx
+        self.handle = handle
+
+    def close(self) -> None:
+        if getattr(self, "handle", None) is not None:
+            N.lib().qe_join_destroy(self.handle)
+            self.handle = None
+
+    def __del__(self):
+        try:
+            self.close()
+        except Exception:
+            pass
+
+
+def join_build(key: DeviceColumn) -> JoinTable:
+    """qe_join_build over one key column (INT64, INT32, DATE32, UINT8, BOOL or FLOAT64; null keys
+    are left out)."""
+    h = N.C.c_void_p()
+    kc = key.as_c()
+    N.check(N.lib().qe_join_build(key.ctx.handle, N.C.byref(kc), N.C.byref(h)))
+    return JoinTable(key.ctx, h)
+
+
+def join_stats(table: JoinTable):
+    """(non-null build rows, distinct keys, longest run of equal keys, slots)."""
+    v = [N.C.c_int64() for _ in range(4)]
+    N.check(N.lib().qe_join_stats(table.handle, *[N.C.byref(x) for x in v]))
+    return tuple(x.value for x in v)
+
+
+def join_probe(table: JoinTable, key: DeviceColumn, kind: int = N.JOIN_INNER, capacity: Optional[int] = None):
+    """qe_join_probe: the (probe row, build row) INT32 index columns of one probe batch, ordered by
+    probe row, then build row; N.JOIN_LEFT pairs an unmatched row with -1. The first try sizes the
+    outputs at `capacity` rows (default: the batch's rows, which a build side of unique keys never
+    exceeds); a short one is carved again at the exact count the call reported: two tries at most."""
+    ctx = key.ctx
+    cap = key.length if capacity is None else int(capacity)
+    kc = key.as_c()
+    pairs = N.C.c_int64()
+    for attempt in range(2):
+        pi = DeviceColumn.empty(N.TYPE_INT32, cap, False, ctx=ctx)
+        bi = DeviceColumn.empty(N.TYPE_INT32, cap, False, ctx=ctx)
+        pc, bc = pi.as_c(), bi.as_c()
+        st = N.lib().qe_join_probe(table.handle, N.C.byref(kc), int(kind), N.C.byref(pc), N.C.byref(bc), N.C.byref(pairs))
+        if st == N.QE_ERR_CAPACITY and attempt == 0:
+            cap = pairs.value
+            continue
+        N.check(st)
+        pi.length = bi.length = pairs.value
+        return pi, bi
+    raise AssertionError("unreachable")
+
+
+def join_probe_mask(table: JoinTable, key: DeviceColumn, anti: bool = False) -> DeviceColumn:
+    """qe_join_probe_mask: BOOL mask of the probe rows that have a match (anti: that have none; a
+    null key has none). Stream-ordered."""
+    mask = DeviceColumn.empty(N.TYPE_BOOL, key.length, False, ctx=key.ctx)
+    kc, mc = key.as_c(), mask.as_c()
+    N.check(N.lib().qe_join_probe_mask(table.handle, N.C.byref(kc), 1 if anti else 0, N.C.byref(mc)))
+    return mask
+
+
+def _taken_bytes(indices: DeviceColumn, cols: Sequence[DeviceColumn]) -> List[Optional[int]]:
+    """Per UTF8 column the value bytes a take by `indices` writes: the sum of the taken lengths
+    (indices repeat in a join, so the input's byte count is no bound). -1 takes nothing."""
+    import torch
+
+    out: List[Optional[int]] = []
+    idx = indices.values[: indices.length].to(torch.int64)
+    hit = idx >= 0
+    idx = idx.clamp(min=0)
+    for c in cols:
+        if c.type != N.TYPE_UTF8 or indices.length == 0 or c.length == 0:
+            out.append(0 if c.type == N.TYPE_UTF8 else None)
+            continue
+        lens = (c.offsets[1: c.length + 1] - c.offsets[: c.length]).to(torch.int64)
+        out.append(int((lens[idx] * hit).sum().item()))
+    return out
+
+
+def _and_validity(cols: Sequence[DeviceColumn]):
+    """The AND of the columns' validity bitmaps (None: no column is nullable)."""
+    v = None
+    for c in cols:
+        if c.validity is not None:
+            v = c.validity.clone() if v is None else v & c.validity
+    return v
+
+
+class _JoinKeyEncoder:
+    """Turns the key columns of either side into the one fixed-width key column qe_join_* takes. One
+    fixed-width key passes through. A lone UTF8 key becomes wide INT64 dictionary codes; several keys
+    become one INT32 key-tuple code (UTF8 members through INT32 string codes first) whose validity is
+    the AND of the members': a null in any member matches nothing. The dictionaries, one per key
+    position, are shared by both sides, so equal values get equal codes; values only the probe side
+    has get fresh codes that match nothing."""
+
+    def __init__(self, ctx, types: Sequence[int]):
+        from .strdict import StringDictionary
+
+        self.ctx = ctx
+        self.types = list(types)
+        self.lone_utf8 = len(self.types) == 1 and self.types[0] == N.TYPE_UTF8
+        self.strings = {}
+        self.tuples = None
+        if self.lone_utf8:
+            self.strings[0] = StringDictionary(ctx, wide=True)
+        elif len(self.types) > 1:
+            for k, t in enumerate(self.types):
+                if t == N.TYPE_UTF8:
+                    self.strings[k] = StringDictionary(ctx)
+            self.tuples = StringDictionary(ctx)
+
+    def encode(self, cols: Sequence[DeviceColumn]) -> DeviceColumn:
+        for k, (c, t) in enumerate(zip(cols, self.types)):
+            if not isinstance(c, DeviceColumn):
+                raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "a join key must evaluate to a column")
+            if len(self.types) > 1 and c.type != t:
+                raise N.IllegalArgumentException(
+                    N.QE_ERR_INVALID_ARG, f"join key {k}: types {c.type} and {t} differ (composite keys pair equal types)")
+        n = cols[0].length
+        if len(cols) == 1 and not self.lone_utf8:
+            return cols[0]
+        if self.lone_utf8:
+            if cols[0].type != N.TYPE_UTF8:
+                raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG, "a UTF8 join key pairs only with UTF8")
+            if n == 0:
+                return DeviceColumn.empty(N.TYPE_INT64, 0, False, ctx=self.ctx)
+            return self.strings[0].encode(cols[0])
+        if n == 0:
+            return DeviceColumn.empty(N.TYPE_INT32, 0, False, ctx=self.ctx)
+        members = [self.strings[k].encode(c) if k in self.strings else c for k, c in enumerate(cols)]
+        codes = self.tuples.encode_tuple(members)
+        return DeviceColumn(N.TYPE_INT32, n, codes.values, _and_validity(cols), None, self.ctx)
+
+    def close(self) -> None:
+        for d in list(self.strings.values()) + ([self.tuples] if self.tuples is not None else []):
+            d.close()
+
+
+class HashJoinExec(PhysicalPlan):
+    """Equi-join (build-defined; the reference's SQL has no JOIN). `on`: 1..MAX_KEYS pairs
+    (left Expression, right Expression); kind: inner, left, semi or anti. The RIGHT child is the build
+    side: drained once into one batch (concat_batches) and hashed (qe_join_build). The LEFT child
+    streams: one output batch per input batch, rows in probe order and, within a probe row, in build
+    row order. A null key matches nothing.
+    Schema: inner / left: the left fields then the right fields (all null for an unmatched row of
+    left); semi / anti: the left fields. An empty build side gives 0-row batches (inner, semi),
+    all-null right columns (left) or every row (anti)."""
+
+    KINDS = ("inner", "left", "semi", "anti")
+
+    def __init__(self, left: PhysicalPlan, right: PhysicalPlan, on, kind: str = "inner"):
+        on = list(on)
+        if not 1 <= len(on) <= N.MAX_KEYS:
+            raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG, f"a join takes 1..{N.MAX_KEYS} key pairs")
+        if kind not in self.KINDS:
+            raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG, f"join kind {kind!r} (one of {self.KINDS})")
+        self.left = left
+        self.right = right
+        self.on = [(le, re) for le, re in on]
+        self.kind = kind
+
+    def schema(self) -> Schema:
+        if self.kind in ("semi", "anti"):
+            return self.left.schema()
+        return Schema(list(self.left.schema().fields) + list(self.right.schema().fields))
+
+    def children(self) -> List[PhysicalPlan]:
+        return [self.left, self.right]
+
+    def _build_batch(self) -> RecordBatch:
+        from .columnar import Context, concat_batches
+
+        batches = [b for b in self.right.execute() if b.fields]
+        for b in batches:
+            for c in b.fields:
+                if not isinstance(c, DeviceColumn):
+                    raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "join input must be device columns")
+        if batches:
+            return concat_batches(batches)
+        ctx = Context.get(0)
+        schema = self.right.schema()
+        return RecordBatch(schema, [
+            DeviceColumn.from_strings([], ctx=ctx) if f.dataType == N.TYPE_UTF8
+            else DeviceColumn.empty(f.dataType, 0, False, ctx=ctx) for f in schema.fields])
+
+    def execute(self) -> Iterator[RecordBatch]:
+        schema = self.schema()
+        build = self._build_batch()
+        build_keys = [re.evaluate(build) for _, re in self.on]
+        for k in build_keys:
+            if not isinstance(k, DeviceColumn):
+                raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "a join key must evaluate to a column")
+        enc = _JoinKeyEncoder(build_keys[0].ctx, [k.type for k in build_keys])
+        table = None
+        try:
+            table = join_build(enc.encode(build_keys))
+            for batch in self.left.execute():
+                for c in batch.fields:
+                    if not isinstance(c, DeviceColumn):
+                        raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "join input must be device columns")
+                key = enc.encode([le.evaluate(batch) for le, _ in self.on])
+                if self.kind in ("semi", "anti"):
+                    yield filter_batch(batch, join_probe_mask(table, key, anti=self.kind == "anti"))
+                    continue
+                left = self.kind == "left"
+                pi, bi = join_probe(table, key, N.JOIN_LEFT if left else N.JOIN_INNER)
+                lcols = take(pi, batch.fields, _taken_bytes(pi, batch.fields))
+                rcols = (take_or_null if left else take)(bi, build.fields, _taken_bytes(bi, build.fields))
+                yield RecordBatch(schema, lcols + rcols)
+        finally:
+            if table is not None:
+                table.close()
+            enc.close()
+
+    def __repr__(self) -> str:
+        return f"HashJoinExec: kind={self.kind}, on={self.on}"
 
 
 class SortExec(PhysicalPlan):
