@@ -38,6 +38,20 @@ def split_records(data: bytes) -> List[bytes]:
     return recs
 
 
+def record_cut(data: bytes) -> int:
+    """End (index + 1) of the last record terminator outside quotes, 0 without one: where a chunk
+    of a larger file is cut (qe_csv_consumed under QE_CSV_PARTIAL_TAIL). Terminators as in
+    split_records: a '\\r' that is the last byte counts."""
+    cut, inq, n = 0, False, len(data)
+    for i in range(n):
+        c = data[i]
+        if c == 0x22:
+            inq = not inq
+        elif not inq and (c == 0x0A or (c == 0x0D and (i + 1 >= n or data[i + 1] != 0x0A))):
+            cut = i + 1
+    return cut
+
+
 def kept(rec: bytes) -> bool:
     return len(rec) > 0 and rec[0] != 0x23 and any(b > 0x20 for b in rec)
 
@@ -91,6 +105,13 @@ def parse(data: bytes, has_header: bool = True):
         names = [f"field_{i + 1}" for i in range(len(first))]
         body = recs
     return names, delim, [[value(f) for f in split_fields(r, delim)] for r in body]
+
+
+def rows(data: bytes, delim: int = 0x2C, has_header: bool = True) -> List[List[bytes]]:
+    """Rows (all fields, as byte values) under an explicit delimiter: parse() without the
+    detection, for inputs whose first kept record must not choose it."""
+    recs = [r for r in split_records(data) if kept(r)]
+    return [[value(f) for f in split_fields(r, delim)] for r in recs[1 if has_header else 0:]]
 
 
 def project(rows: List[List[bytes]], idx: Sequence[int]) -> List[List[str]]:
