@@ -197,7 +197,11 @@ int qe_eval_arith(qe_ctx* ctx, int32_t op, const qe_operand* lhs, const qe_opera
 
 /* Comparison (K2) -> QE_TYPE_BOOL bitmap. Signed int64 / IEEE fp64 (NaN: only NE true),
  * mixed int64/fp64 compares as fp64; UTF8 supports EQ/NE against a UTF8 literal column of
- * length 1 (byte equality). out->values: ceil(length/8) bytes. */
+ * length 1 (byte equality). out->values: ceil(length/8) bytes, the padding bits of the last
+ * byte 0; the value bit of a null row is unspecified. Null in -> null out, and a null literal
+ * gives an all-null result: a qe_scalar with is_null set, or a one-row UTF8 literal column whose
+ * validity bit is clear (which does not compare as ""). out->validity is required iff an operand
+ * can be null (a UTF8 literal column counts only when its row is null). */
 int qe_eval_cmp(qe_ctx* ctx, int32_t op, const qe_operand* lhs, const qe_operand* rhs,
                 qe_column* out);
 

@@ -36,12 +36,39 @@ def _valid(v: Optional[np.ndarray], n: int) -> np.ndarray:
     return np.ones(n, dtype=bool) if v is None else np.asarray(v, dtype=bool)
 
 
+class NullLiteral:
+    """A null literal operand of K1 / K2 (qe_scalar.is_null): typed, because a null FLOAT64 literal
+    still promotes the result to fp64. Every row of the result is null."""
+
+    def __init__(self, is_f64: bool):
+        self.is_f64 = is_f64
+
+
+NULL_I64, NULL_F64 = NullLiteral(False), NullLiteral(True)
+
+
+def _is_f64(x) -> bool:
+    if isinstance(x, NullLiteral):
+        return x.is_f64
+    return isinstance(x, float) or np.asarray(x).dtype == np.float64
+
+
+def _null_literal_rows(a, b):
+    """Row count when one operand is a null literal, else None."""
+    if isinstance(a, NullLiteral) or isinstance(b, NullLiteral):
+        return len(b) if isinstance(a, NullLiteral) else len(a)
+    return None
+
+
 # ---- K1 arithmetic (build-defined: JVM Long wrap, truncating division, x/0 -> null) ---------------
 def arith(op: int, a, av, b, bv) -> Tuple[np.ndarray, np.ndarray]:
-    """a/b: ndarray or python scalar (literal). Returns (values, valid)."""
+    """a/b: ndarray, python scalar (literal) or NullLiteral. Returns (values, valid). Narrow integer
+    columns (int32, uint8) widen to int64 by value: sign- and zero-extended."""
+    is_f = _is_f64(a) or _is_f64(b)
+    n = _null_literal_rows(a, b)
+    if n is not None:  # a null literal: every row null, the result type as for a valid one
+        return np.zeros(n, dtype=np.float64 if is_f else np.int64), np.zeros(n, dtype=bool)
     n = len(a) if isinstance(a, np.ndarray) else len(b)
-    is_f = (np.asarray(a).dtype == np.float64) or (np.asarray(b).dtype == np.float64) \
-        or isinstance(a, float) or isinstance(b, float)
     valid = _valid(av, n) & _valid(bv, n)
     if is_f:
         x = np.broadcast_to(np.asarray(a, dtype=np.float64), (n,))
@@ -73,10 +100,12 @@ def arith(op: int, a, av, b, bv) -> Tuple[np.ndarray, np.ndarray]:
 
 # ---- K2 comparison (IEEE fp64: NaN -> only NE true; signed int64; UTF-8 byte equality) -----------
 def cmp(op: int, a, av, b, bv) -> Tuple[np.ndarray, np.ndarray]:
+    n = _null_literal_rows(a, b)
+    if n is not None:  # a null literal: every row null
+        return np.zeros(n, dtype=bool), np.zeros(n, dtype=bool)
     n = len(a) if isinstance(a, np.ndarray) else len(b)
     valid = _valid(av, n) & _valid(bv, n)
-    is_f = (np.asarray(a).dtype == np.float64) or (np.asarray(b).dtype == np.float64) \
-        or isinstance(a, float) or isinstance(b, float)
+    is_f = _is_f64(a) or _is_f64(b)
     dt = np.float64 if is_f else np.int64
     x = np.broadcast_to(np.asarray(a, dtype=dt), (n,))
     y = np.broadcast_to(np.asarray(b, dtype=dt), (n,))
@@ -85,9 +114,17 @@ def cmp(op: int, a, av, b, bv) -> Tuple[np.ndarray, np.ndarray]:
     return r & valid, valid
 
 
-def cmp_utf8(op: int, strings: Sequence[Optional[str]], lit: str) -> Tuple[np.ndarray, np.ndarray]:
+def _utf8(s) -> bytes:
+    return s if isinstance(s, bytes) else s.encode()
+
+
+def cmp_utf8(op: int, strings: Sequence[Any], lit: Any) -> Tuple[np.ndarray, np.ndarray]:
+    """strings / lit: str or bytes (byte equality; the bytes need not be well-formed UTF-8), None =
+    null. A null literal gives an all-null result, as a null numeric literal does."""
+    if lit is None:
+        return np.zeros(len(strings), dtype=bool), np.zeros(len(strings), dtype=bool)
     valid = np.array([s is not None for s in strings], dtype=bool)
-    eq = np.array([s is not None and s.encode() == lit.encode() for s in strings], dtype=bool)
+    eq = np.array([s is not None and _utf8(s) == _utf8(lit) for s in strings], dtype=bool)
     r = eq if op == OP_EQ else (~eq & valid)
     return r, valid
 

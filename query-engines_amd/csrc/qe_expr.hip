@@ -352,8 +352,20 @@ int qe_eval_cmp(qe_ctx* ctx, int32_t op, const qe_operand* lhs, const qe_operand
     QE_CHECK(c->offsets && rhs->col->offsets, QE_ERR_INVALID_ARG, "UTF8 offsets missing");
     QE_CHECK(!c->validity || out->validity, QE_ERR_INVALID_ARG, "output validity buffer required");
     int32_t lo[2];
+    uint8_t lit_valid = 1;
     QE_HIP(hipMemcpyAsync(lo, rhs->col->offsets, 8, hipMemcpyDeviceToHost, ctx->stream));
+    if (rhs->col->validity)
+      QE_HIP(hipMemcpyAsync(&lit_valid, rhs->col->validity, 1, hipMemcpyDeviceToHost, ctx->stream));
     QE_TRY(ctx_sync(ctx));
+    if (!(lit_valid & 1)) {  // a null literal: every row null, as a null numeric literal gives
+      QE_CHECK(out->validity, QE_ERR_INVALID_ARG, "result can be null: output validity buffer required");
+      out->length = n;
+      if (n == 0) return QE_OK;
+      const size_t nbytes = (size_t)((n + 7) >> 3);
+      QE_HIP(hipMemsetAsync(out->values, 0, nbytes, ctx->stream));
+      QE_HIP(hipMemsetAsync(out->validity, 0, nbytes, ctx->stream));
+      return QE_OK;
+    }
     out->length = n;
     if (n == 0) return QE_OK;
     hipLaunchKernelGGL(k_cmp_utf8, dim3(grid_for(ctx, (n + 7) / 8)), dim3(256), 0, ctx->stream, c->offsets,
