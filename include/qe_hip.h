@@ -494,7 +494,11 @@ int qe_hashagg_update_fused(qe_hashagg* agg, const qe_column* cols, int32_t ncol
  * order, as the value of each output program (same token language and null rules as the
  * aggregate inputs; a lone column reference keeps its type, other programs give INT64 or
  * FLOAT64). outs[k]: capacity >= cols[0].length rows, type = the program's type; validity
- * written when non-NULL. *out_count = rows written (also each outs[k].length).
+ * written when non-NULL: the whole bitmap of n = cols[0].length rows, in 32-bit words (ceil(n / 32)
+ * words). Bits [0, count) are the rows' validity; every bit at and past count, the last word's
+ * padding included, is 0 where the output can be null (a program over a nullable column, or a
+ * division) and 1 where it cannot. Value rows at and past count are left as they were.
+ * *out_count = rows written (also each outs[k].length).
  * Needs per-plan kernel specialisation: QE_ERR_UNSUPPORTED when it is off or the shape is
  * outside the generator (callers then run qe_eval_cmp + qe_filter_apply + qe_eval_arith). */
 typedef struct qe_select_spec {
@@ -523,6 +527,28 @@ typedef struct qe_select_pending qe_select_pending;
 int qe_select_project_async(qe_ctx* ctx, const qe_column* cols, int32_t ncols, const qe_select_spec* spec,
                             qe_column* outs, qe_select_pending** pending);
 int qe_select_pending_wait(qe_select_pending* pending, int64_t* out_count);
+/* Measurement hook: how qe_select_project[_async] would run this very call (same arguments; the
+ * environment switches are read as the call reads them). Launches nothing and allocates nothing on
+ * the device. Tests place their selections relative to tile_rows / group_rows / block from here.
+ * A tile is tile_rows consecutive rows; inside it, thread t of `block` holds rows r * block + t.
+ * The resident pass stores a tile in groups of group_rows consecutive rows. length-0 inputs give
+ * scheme 0 and zeros. */
+#define QE_SELECT_SCHEME_RESIDENT 1            /* one register-resident pass */
+#define QE_SELECT_SCHEME_TWOPASS 2             /* count pass, write pass summing earlier counts */
+#define QE_SELECT_SCHEME_SCANNED 3             /* count pass, device scan, write pass */
+#define QE_SELECT_SCHEME_LOOKBACK_PERSISTENT 4 /* one pass, decoupled look-back, persistent grid */
+#define QE_SELECT_SCHEME_LOOKBACK_COUNTER 5    /* ... tiles ordered by a device counter */
+typedef struct qe_select_layout {
+  int32_t scheme; /* QE_SELECT_SCHEME_* */
+  int32_t staged; /* 1: outputs staged in LDS (16-byte stores, validity words), 0: per-lane stores */
+  int32_t block;  /* threads per workgroup */
+  int32_t reserved;
+  int64_t tile_rows;
+  int64_t tiles;
+  int64_t group_rows; /* resident pass: rows per output group, else 0 */
+} qe_select_layout;
+int qe_select_project_layout(qe_ctx* ctx, const qe_column* cols, int32_t ncols, const qe_select_spec* spec,
+                             const qe_column* outs, qe_select_layout* out);
 
 /* Number of groups so far (synchronises). */
 int qe_hashagg_num_groups(qe_hashagg* agg, int64_t* out);

@@ -193,6 +193,11 @@ uint64_t jit_kernel_signature(hipFunction_t fn);  // hash of a specialised kerne
 bool selproj_pipelined();  // look-back modes load the next tile while this one is compacted
 int selproj_rows(const qe::Plan& P, int mode);  // rows per thread of `mode`'s tiles
 bool selproj_nt(const qe::Plan& P);  // non-temporal input loads (large inputs)
+// `mode`'s write pass stages its outputs in LDS (16-byte stores, validity words) rather than
+// storing per lane (emit_selproj_write)
+bool selproj_staged(const qe::Plan& P, const int32_t* out_kind, int nout, int mode);
+// stripes per staged output group of the resident pass at R rows per thread
+inline int selproj_resident_group(int R) { return R < 8 ? R : 8; }
 // Exclusive scan of n int64 on the ctx stream (one block); out[n] = total. (qe_filter.hip)
 int exclusive_scan_i64(qe_ctx* ctx, const int64_t* in, int64_t* out, int64_t n);
 // UTF-8 gather from (source byte offset, length) pairs: length scan, output offsets, byte copy

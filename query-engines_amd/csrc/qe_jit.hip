@@ -2351,19 +2351,23 @@ void emit_selproj_loads(const Plan& P, std::ostringstream& o, unsigned need, boo
   }
 }
 
+bool selproj_staged(const Plan& P, const int32_t* out_kind, int nout, int mode) {
+  bool staged = (size_t)nout * selproj_rows(P, mode) * selproj_block(mode) * 8 <= kSelprojStageBytes;
+  for (int k = 0; k < nout; ++k) staged = staged && (out_kind[k] & 0xFF) == 8;
+  return staged;
+}
+
 // Write phase of one select-project tile, after the caller's code has loaded the tile's columns
 // (c<slot>[R], v<slot>) and computed `act` (bit r: row base + r * BT + t is selected): ballots,
 // per-(stripe, wave) counts, one wave's scan, the tile's output base (decoupled look-back or the
 // two-pass prefix), then the compacted stores.
 bool emit_selproj_write(const Plan& P, const int32_t* out_kind, int nout, int mode, std::ostringstream& o,
                         bool regs = false, const std::string& prefetch = std::string()) {
-  const int R = selproj_rows(P, mode);
   // Staged output (all outputs 8 bytes wide, R x BT x 8 B each within 64 KiB of LDS): selected
   // rows land compacted in LDS, then the tile's output range is written with 16-byte stores, all
   // lanes active. Direct 8-byte stores from the row registers were store-issue bound (half the
   // lanes idle at 50 % selectivity, 16 store instructions per thread).
-  bool staged = (size_t)nout * R * selproj_block(mode) * 8 <= kSelprojStageBytes;
-  for (int k = 0; k < nout; ++k) staged = staged && (out_kind[k] & 0xFF) == 8;
+  const bool staged = selproj_staged(P, out_kind, nout, mode);
   std::vector<Expr> ex(nout);
   for (int k = 0; k < nout; ++k) {
     if (!agg_expr(P, k, &ex[k])) return false;
@@ -2752,7 +2756,7 @@ bool gen_selproj_resident_source(const Plan& P, const int32_t* out_kind, int nou
   std::vector<Expr> ex(nout);
   for (int k = 0; k < nout; ++k)
     if (!agg_expr(P, k, &ex[k])) return false;
-  const int GS = std::min(R, 8);  // stripes per staged output group (<= 128 KiB of LDS; their loads in flight)
+  const int GS = selproj_resident_group(R);  // stripes per staged output group (<= 128 KiB of LDS; their loads in flight)
   std::ostringstream o;
   o << "\nusing namespace qe;\n"
     << "extern \"C\" __global__ void __launch_bounds__(" << kResBlock << ") qe_selproj(const Plan P) {\n"

@@ -126,6 +126,113 @@ int init_validity(qe_ctx* ctx, const qe_column* outs, const int32_t* out_kind, i
   return QE_OK;
 }
 
+// Compiles the call's plan into r: P, the column widths, the output kinds (byte width | 0x100 when
+// the output's validity bits are the kernel's to set) and the output buffers. Host work only.
+int select_plan(const qe_column* cols, int32_t ncols, const qe_select_spec* spec, const qe_column* outs,
+                qe_select_pending* r) {
+  Plan& P = r->P;
+  bool col_f64[QE_MAX_COLS];
+  QE_TRY(compile_inputs(cols, ncols, spec->mask_col, spec->nterms, spec->terms, &P, col_f64));
+  const int64_t n = P.n;
+  for (int c = 0; c < ncols && c < QE_MAX_COLS; ++c) r->col_width[c] = type_width(cols[c].type);
+  bool nullable[QE_MAX_AGGS];
+  P.naggs = spec->nout;
+  r->nout = spec->nout;
+  for (int k = 0; k < spec->nout; ++k) {
+    bool is_f = false;
+    DAgg& a = P.aggs[k];
+    QE_TRY(compile_program(cols, ncols, col_f64, spec->outputs[k], k, &a, &is_f, &nullable[k]));
+    const int32_t t = program_type(cols, a, is_f);
+    QE_CHECK(t != QE_TYPE_BOOL, QE_ERR_UNSUPPORTED, "output %d: BOOL pass-through is not fused", k);
+    QE_CHECK(outs[k].type == t, QE_ERR_INVALID_ARG, "output %d: column type %d, expression yields %d", k, outs[k].type,
+             t);
+    QE_CHECK(outs[k].length >= n && (outs[k].values || n == 0), QE_ERR_CAPACITY,
+             "output %d: capacity %lld rows, input has %lld", k, (long long)outs[k].length, (long long)n);
+    r->out_kind[k] = type_width(t) | ((nullable[k] && outs[k].validity) ? 0x100 : 0);
+    P.t.acc[k] = (qi64*)outs[k].values;
+    P.t.nn[k] = (qu64*)outs[k].validity;
+    r->outs[k] = outs[k];
+  }
+  return QE_OK;
+}
+
+// How one select-project over P runs: the tile-base scheme and its tile geometry. Decided here and
+// nowhere else: launch_select launches what this says, qe_select_project_layout reports it.
+struct SelectLayout {
+  int scheme = 0;      // QE_SELECT_SCHEME_*
+  int mode = 0;        // SP_* of the (write) kernel
+  int R = 0;           // rows per thread
+  int block = 0;       // threads per workgroup
+  int64_t tiles = 0;   // tiles of R x block rows
+  int64_t grid = 0;    // resident pass: workgroups (tiles > grid: several rounds)
+  bool staged = false; // outputs staged in LDS
+};
+
+// Launches nothing and allocates nothing. `persist_ok` = false forces counter-ordered tiles (the
+// rerun after a stall), `resident_ok` = false the modes other than the resident pass.
+int select_layout(const qe_ctx* ctx, const Plan& P, const int32_t* col_width, const int32_t* out_kind, int nout,
+                  bool persist_ok, bool resident_ok, SelectLayout* L) {
+  *L = SelectLayout();
+  const int64_t n = P.n;
+  if (n == 0) return QE_OK;
+  // One register-resident pass (SP_RESIDENT, qe_jit.hip gen_selproj_resident_source) while every
+  // workgroup's predicate columns fit its registers: ~10M rows of one 8-byte predicate column.
+  // QE_SELPROJ_TWOPASS (any value) picks the other modes, QE_SELPROJ_RESIDENT=0 turns it off.
+  const char* tpe = getenv("QE_SELPROJ_TWOPASS");  // read per call: tests switch it
+  const int rres = (resident_ok && !(tpe && *tpe)) ? selproj_resident_rows(P, out_kind, nout, n, ctx->num_cus) : 0;
+  // tiles of R x 1024 rows, one workgroup per CU walking them in rounds (one round up to ~12M rows)
+  const int64_t rtiles = rres ? (int64_t)div_up((uint64_t)n, (uint64_t)rres * 1024) : 0;
+  const int64_t rgrid = std::min<int64_t>(rtiles, ctx->num_cus);
+  if (rres && rgrid <= 256) {
+    L->scheme = QE_SELECT_SCHEME_RESIDENT;
+    L->mode = SP_RESIDENT;
+    L->R = rres;
+    L->block = 1024;
+    L->tiles = rtiles;
+    L->grid = rgrid;
+    L->staged = true;
+    return QE_OK;
+  }
+  // Two passes (count per tile, then write at the sum of the earlier tiles' counts) while the
+  // predicate's columns fit the MALL, so the second pass reads them from there: no look-back
+  // round trips. QE_SELPROJ_TWOPASS=0/1 forces either way.
+  const int twopass_env = tpe && *tpe ? (tpe[0] == '1' ? 1 : tpe[0] == '2' ? 2 : 0) : -1;
+  unsigned pred_cols = P.mask_col >= 0 ? 1u << P.mask_col : 0u;
+  for (int t = 0; t < P.nterms; ++t)
+    pred_cols |= (1u << P.terms[t].lhs) | (P.terms[t].rhs >= 0 ? 1u << P.terms[t].rhs : 0u);
+  size_t pred_bytes = 0;
+  for (int c = 0; c < P.ncols; ++c)
+    if ((pred_cols >> c) & 1u) pred_bytes += (size_t)n * std::max(1, col_width[c]);
+  // (each write-pass tile sums all earlier tiles' counts, so the tile count is bounded too: a
+  // plan with no predicate reads nothing in the count pass but still pays the prefix sums)
+  const int R2 = selproj_rows(P, SP_COUNT);  // two-pass tiles
+  const int64_t tiles2 = (int64_t)div_up((uint64_t)n, (uint64_t)R2 * selproj_block(SP_COUNT));
+  const bool twopass = twopass_env >= 0 ? twopass_env == 1 : (pred_bytes <= (96ull << 20) && tiles2 <= 4096);
+  // Scanned two passes (QE_SELPROJ_TWOPASS=2): count pass, a device scan of the tile counts, then
+  // the write pass reads its tile's base — no look-back chain and no per-tile prefix sums, at the
+  // price of reading the predicate's columns twice.
+  const bool scanned = twopass_env == 2;
+  // the look-back modes (persistent and its counter-ordered rerun) share one tile size
+  const bool two = twopass || scanned;
+  // Tile order of the look-back: a persistent grid (every workgroup resident, tiles assigned
+  // statically) or one tile per workgroup with ids from a device counter in start order
+  // (QE_SELPROJ_PERSIST=0). The counter is one word every workgroup hits: ~88 returning atomics/us,
+  // a floor of 2.8 ms for 1B rows in 4096-row tiles.
+  static const bool persist_env = [] {
+    const char* e = getenv("QE_SELPROJ_PERSIST");
+    return !(e && e[0] == '0');
+  }();
+  L->mode = scanned ? SP_WRITE_SCAN : twopass ? SP_WRITE : (persist_env && persist_ok) ? SP_PERSIST : SP_COUNTER;
+  L->scheme = scanned ? QE_SELECT_SCHEME_SCANNED : twopass ? QE_SELECT_SCHEME_TWOPASS
+            : L->mode == SP_PERSIST ? QE_SELECT_SCHEME_LOOKBACK_PERSISTENT : QE_SELECT_SCHEME_LOOKBACK_COUNTER;
+  L->R = two ? R2 : selproj_rows(P, SP_PERSIST);
+  L->block = selproj_block(two ? SP_COUNT : SP_PERSIST);  // (SP_COUNTER shares SP_PERSIST's)
+  L->tiles = (int64_t)div_up((uint64_t)n, (uint64_t)L->R * L->block);
+  QE_CHECK(L->tiles < (1ll << 31), QE_ERR_CAPACITY, "too many rows for one select-project call");
+  L->staged = selproj_staged(P, out_kind, nout, L->mode);
+  return QE_OK;
+}
+
 // Queues the kernels of one select-project over P (validity already initialised) and the copy of
 // its count into pin[0] (pin[1]: 1 if a persistent look-back tile never saw its predecessor).
 // `persist_ok` = false forces counter-ordered tiles (the rerun after a stall).
@@ -133,17 +240,12 @@ int launch_select(qe_ctx* ctx, Plan& P, const int32_t* col_width, const int32_t*
                   uint64_t* pin, bool* persist_used, bool* poll, bool resident_ok = true) {
   *persist_used = false;
   *poll = false;
-  const int64_t n = P.n;
-  if (n == 0) return QE_OK;  // pin[] was zeroed by the caller
-  // One register-resident pass (SP_RESIDENT, qe_jit.hip gen_selproj_resident_source) while every
-  // workgroup's predicate columns fit its registers: ~10M rows of one 8-byte predicate column.
-  // QE_SELPROJ_TWOPASS (any value) picks the other modes, QE_SELPROJ_RESIDENT=0 turns it off.
-  const char* tpe0 = getenv("QE_SELPROJ_TWOPASS");
-  const int rres = (resident_ok && !(tpe0 && *tpe0)) ? selproj_resident_rows(P, out_kind, nout, n, ctx->num_cus) : 0;
-  // tiles of R x 1024 rows, one workgroup per CU walking them in rounds (one round up to ~12M rows)
-  const int64_t rtiles = rres ? (int64_t)div_up((uint64_t)n, (uint64_t)rres * 1024) : 0;
-  const int64_t rgrid = std::min<int64_t>(rtiles, ctx->num_cus);
-  if (rres && rgrid <= 256) {
+  if (P.n == 0) return QE_OK;  // pin[] was zeroed by the caller
+  SelectLayout L;
+  QE_TRY(select_layout(ctx, P, col_width, out_kind, nout, persist_ok, resident_ok, &L));
+  if (L.scheme == QE_SELECT_SCHEME_RESIDENT) {
+    const int rres = L.R;
+    const int64_t rtiles = L.tiles, rgrid = L.grid;
     // status words: 256 per-workgroup "prefixes taken" + one total per tile, epoch-tagged
     const size_t need = (size_t)(256 + rtiles) * 8;
     if (need > ctx->sp_status_bytes) {
@@ -180,50 +282,19 @@ int launch_select(qe_ctx* ctx, Plan& P, const int32_t* col_width, const int32_t*
     *poll = true;
     return QE_OK;
   }
-  // Tile order: a persistent grid (every workgroup resident, tiles assigned statically) or one
-  // tile per workgroup with ids from a device counter in start order (QE_SELPROJ_PERSIST=0). The
-  // counter is one word every workgroup hits: ~88 returning atomics/us, a floor of 2.8 ms for
-  // 1B rows in 4096-row tiles. Residency comes from the grid size alone, and the occupancy query
+  // Residency of the persistent grid comes from the grid size alone, and the occupancy query
   // is advisory (it can over-report by a block per CU), so the persistent grid keeps at most
   // min(4, occupancy - 1) blocks per CU, and its look-back spins are bounded: a tile whose
   // predecessor never publishes flags ctl[2], and the call reruns with counter-ordered tiles.
-  static const bool persist_env = [] {
-    const char* e = getenv("QE_SELPROJ_PERSIST");
-    return !(e && e[0] == '0');
-  }();
   static const int wg_cap = [] {
     const char* e = getenv("QE_SELPROJ_WG_PER_CU");
     return e && *e ? std::max(1, atoi(e)) : 4;
   }();
-  // Two passes (count per tile, then write at the sum of the earlier tiles' counts) while the
-  // predicate's columns fit the MALL, so the second pass reads them from there: no look-back
-  // round trips. QE_SELPROJ_TWOPASS=0/1 forces either way.
-  const char* tpe = getenv("QE_SELPROJ_TWOPASS");  // read per call: tests switch it
-  const int twopass_env = tpe && *tpe ? (tpe[0] == '1' ? 1 : tpe[0] == '2' ? 2 : 0) : -1;
-  unsigned pred_cols = P.mask_col >= 0 ? 1u << P.mask_col : 0u;
-  for (int t = 0; t < P.nterms; ++t)
-    pred_cols |= (1u << P.terms[t].lhs) | (P.terms[t].rhs >= 0 ? 1u << P.terms[t].rhs : 0u);
-  size_t pred_bytes = 0;
-  for (int c = 0; c < P.ncols; ++c)
-    if ((pred_cols >> c) & 1u) pred_bytes += (size_t)n * std::max(1, col_width[c]);
-  // (each write-pass tile sums all earlier tiles' counts, so the tile count is bounded too: a
-  // plan with no predicate reads nothing in the count pass but still pays the prefix sums)
-  const int R2 = selproj_rows(P, SP_COUNT);  // two-pass tiles
-  const int64_t tiles2 = (int64_t)div_up((uint64_t)n, (uint64_t)R2 * selproj_block(SP_COUNT));
-  const bool twopass = twopass_env >= 0 ? twopass_env == 1 : (pred_bytes <= (96ull << 20) && tiles2 <= 4096);
-  // the look-back modes (persistent and its counter-ordered rerun) share one tile size
-  const bool two = twopass || twopass_env == 2;
-  const int R = two ? R2 : selproj_rows(P, SP_PERSIST);
-  const int BT = selproj_block(two ? SP_COUNT : SP_PERSIST);  // (SP_COUNTER shares SP_PERSIST's)
-  const int64_t tiles = (int64_t)div_up((uint64_t)n, (uint64_t)R * BT);
-  QE_CHECK(tiles < (1ll << 31), QE_ERR_CAPACITY, "too many rows for one select-project call");
-  // Scanned two passes (QE_SELPROJ_TWOPASS=2): count pass, a device scan of the tile counts, then
-  // the write pass reads its tile's base — no look-back chain and no per-tile prefix sums, at the
-  // price of reading the predicate's columns twice.
-  const bool scanned = twopass_env == 2;
+  const int BT = L.block;
+  const int64_t tiles = L.tiles;
   hipFunction_t fn;
   int bpc = 0;
-  if (scanned) {
+  if (L.scheme == QE_SELECT_SCHEME_SCANNED) {
     void* s;
     QE_TRY(ctx_scratch(ctx, (size_t)(2 * tiles + 4) * 8, &s));
     qu64* ctl = (qu64*)s;
@@ -246,7 +317,7 @@ int launch_select(qe_ctx* ctx, Plan& P, const int32_t* col_width, const int32_t*
   // the kernels write the count (and the stall flag) straight into the pinned words: no copy
   // command behind them on the stream
   P.host_ctl = (qu64*)pin;
-  if (twopass) {
+  if (L.scheme == QE_SELECT_SCHEME_TWOPASS) {
     void* s;
     QE_TRY(ctx_scratch(ctx, (size_t)(tiles + 3) * 8, &s));
     qu64* ctl = (qu64*)s;
@@ -268,8 +339,8 @@ int launch_select(qe_ctx* ctx, Plan& P, const int32_t* col_width, const int32_t*
   P.t.ctl = ctl;
   P.t.keys = (qi64*)(ctl + 3);
   P.t.cap = (qu64)tiles;
-  const bool persist = persist_env && persist_ok;
-  const int mode = persist ? SP_PERSIST : SP_COUNTER;
+  const bool persist = L.mode == SP_PERSIST;
+  const int mode = L.mode;
   QE_TRY(selproj_kernel(ctx, P, out_kind, nout, mode, &fn, &bpc));
   // QE_SELPROJ_OVERSUB (tests only) multiplies the persistent grid past residency, to exercise
   // the bounded look-back and the rerun
@@ -357,28 +428,8 @@ int qe_select_project_async(qe_ctx* ctx, const qe_column* cols, int32_t ncols, c
   std::unique_ptr<qe_select_pending> r(new qe_select_pending());
   r->ctx = ctx;
   Plan& P = r->P;
-  bool col_f64[QE_MAX_COLS];
-  QE_TRY(compile_inputs(cols, ncols, spec->mask_col, spec->nterms, spec->terms, &P, col_f64));
+  QE_TRY(select_plan(cols, ncols, spec, outs, r.get()));
   const int64_t n = P.n;
-  for (int c = 0; c < ncols && c < QE_MAX_COLS; ++c) r->col_width[c] = type_width(cols[c].type);
-  bool nullable[QE_MAX_AGGS];
-  P.naggs = spec->nout;
-  r->nout = spec->nout;
-  for (int k = 0; k < spec->nout; ++k) {
-    bool is_f = false;
-    DAgg& a = P.aggs[k];
-    QE_TRY(compile_program(cols, ncols, col_f64, spec->outputs[k], k, &a, &is_f, &nullable[k]));
-    const int32_t t = program_type(cols, a, is_f);
-    QE_CHECK(t != QE_TYPE_BOOL, QE_ERR_UNSUPPORTED, "output %d: BOOL pass-through is not fused", k);
-    QE_CHECK(outs[k].type == t, QE_ERR_INVALID_ARG, "output %d: column type %d, expression yields %d", k, outs[k].type,
-             t);
-    QE_CHECK(outs[k].length >= n && (outs[k].values || n == 0), QE_ERR_CAPACITY,
-             "output %d: capacity %lld rows, input has %lld", k, (long long)outs[k].length, (long long)n);
-    r->out_kind[k] = type_width(t) | ((nullable[k] && outs[k].validity) ? 0x100 : 0);
-    P.t.acc[k] = (qi64*)outs[k].values;
-    P.t.nn[k] = (qu64*)outs[k].validity;
-    r->outs[k] = outs[k];
-  }
   if (!ctx->jit) return fail(QE_ERR_UNSUPPORTED, "fused select-project needs kernel specialisation (jit is off)");
   hprof(1);
   QE_TRY(pinned_slot_alloc(&r->pin));
@@ -400,6 +451,26 @@ int qe_select_project_async(qe_ctx* ctx, const qe_column* cols, int32_t ncols, c
   hprof(5);
   if (g_hprof.on) ++g_hprof.n;
   *pending = r.release();
+  return QE_OK;
+}
+
+int qe_select_project_layout(qe_ctx* ctx, const qe_column* cols, int32_t ncols, const qe_select_spec* spec,
+                             const qe_column* outs, qe_select_layout* out) {
+  QE_TRY(ctx_enter(ctx));
+  QE_CHECK(cols && spec && outs && out, QE_ERR_INVALID_ARG, "null argument");
+  QE_CHECK(spec->nout >= 1 && spec->nout <= QE_MAX_AGGS, QE_ERR_UNSUPPORTED, "select-project takes 1..%d outputs",
+           QE_MAX_AGGS);
+  memset(out, 0, sizeof *out);
+  std::unique_ptr<qe_select_pending> r(new qe_select_pending());
+  QE_TRY(select_plan(cols, ncols, spec, outs, r.get()));
+  SelectLayout L;
+  QE_TRY(select_layout(ctx, r->P, r->col_width, r->out_kind, r->nout, true, true, &L));
+  out->scheme = L.scheme;
+  out->staged = L.staged ? 1 : 0;
+  out->block = L.block;
+  out->tile_rows = (int64_t)L.R * L.block;
+  out->tiles = L.tiles;
+  out->group_rows = L.scheme == QE_SELECT_SCHEME_RESIDENT ? (int64_t)selproj_resident_group(L.R) * L.block : 0;
   return QE_OK;
 }
 

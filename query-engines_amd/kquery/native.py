@@ -180,6 +180,22 @@ class QeSelectSpec(C.Structure):
     ]
 
 
+SELECT_RESIDENT, SELECT_TWOPASS, SELECT_SCANNED, SELECT_LOOKBACK_PERSISTENT, SELECT_LOOKBACK_COUNTER = 1, 2, 3, 4, 5
+
+
+class QeSelectLayout(C.Structure):
+    """qe_select_project_layout's report (QE_SELECT_SCHEME_*)."""
+    _fields_ = [
+        ("scheme", C.c_int32),
+        ("staged", C.c_int32),
+        ("block", C.c_int32),
+        ("reserved", C.c_int32),
+        ("tile_rows", C.c_int64),
+        ("tiles", C.c_int64),
+        ("group_rows", C.c_int64),
+    ]
+
+
 # ---- library ------------------------------------------------------------------------------------
 _lib = None
 
@@ -289,6 +305,8 @@ SIGNATURES = [
     ("qe_hash_partition", C.c_int, [_P, _COLP, C.c_int32, C.c_int32, _P]),
     ("qe_select_project", C.c_int, [_P, _COLP, C.c_int32, C.POINTER(QeSelectSpec), _COLP, _I64P]),
     ("qe_select_project_async", C.c_int, [_P, _COLP, C.c_int32, C.POINTER(QeSelectSpec), _COLP, C.POINTER(_P)]),
+    ("qe_select_project_layout", C.c_int, [_P, _COLP, C.c_int32, C.POINTER(QeSelectSpec), _COLP,
+                                           C.POINTER(QeSelectLayout)]),
     ("qe_select_pending_wait", C.c_int, [_P, _I64P]),
     ("qe_csv_parse", C.c_int, [_P, _P, C.c_int64, C.POINTER(QeCsvOptions), _PP]),
     ("qe_csv_rows", C.c_int, [_P, _I64P]),

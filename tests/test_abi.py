@@ -36,10 +36,12 @@ def test_measurement_hooks_are_declared_and_bound():
     lib = N.load_library()
     sigs = {s[0]: s for s in N.SIGNATURES}
     for name in ("qe_hashagg_last_kernel_time", "qe_hashagg_last_kernel_signature", "qe_hashagg_last_kernel_kind",
-                 "qe_hashagg_last_chunk_stats"):
+                 "qe_hashagg_last_chunk_stats", "qe_sort_layout", "qe_select_project_layout"):
         assert name in _declared_functions() and hasattr(lib, name)
     _, res, args = sigs["qe_hashagg_last_chunk_stats"]
     assert res is C.c_int and args[1:] == [C.POINTER(C.c_int64)] * 3
+    _, res, args = sigs["qe_select_project_layout"]
+    assert res is C.c_int and args[-1] is C.POINTER(N.QeSelectLayout)
 
 
 def test_abi_version_and_error_string():
@@ -67,7 +69,8 @@ int main(void){
    sizeof(qe_fused_spec));
  printf("%zu %zu %zu %zu\n", offsetof(qe_fused_spec, terms), offsetof(qe_fused_spec, key_cols),
    offsetof(qe_fused_spec, inputs), offsetof(qe_global_agg, avg));
- printf("%zu %zu\n", sizeof(qe_select_spec), offsetof(qe_select_spec, outputs));
+ printf("%zu %zu %zu %zu %zu\n", sizeof(qe_select_spec), offsetof(qe_select_spec, outputs), sizeof(qe_select_layout),
+   offsetof(qe_select_layout, tile_rows), offsetof(qe_select_layout, group_rows));
  printf("%zu %zu %zu %zu %zu\n", sizeof(struct ArrowSchema), sizeof(struct ArrowArray),
    sizeof(struct ArrowDeviceArray), offsetof(struct ArrowDeviceArray, device_type),
    offsetof(struct ArrowDeviceArray, sync_event));
@@ -88,7 +91,8 @@ int main(void){
     from kquery import arrow_io as A
 
     sel = [int(x) for x in out[2].split()]
-    assert sel == [C.sizeof(N.QeSelectSpec), N.QeSelectSpec.outputs.offset]
+    assert sel == [C.sizeof(N.QeSelectSpec), N.QeSelectSpec.outputs.offset, C.sizeof(N.QeSelectLayout),
+                   N.QeSelectLayout.tile_rows.offset, N.QeSelectLayout.group_rows.offset]
     arrow = [int(x) for x in out[3].split()]
     assert arrow == [C.sizeof(A.ArrowSchemaC), C.sizeof(A.ArrowArrayC), C.sizeof(A.ArrowDeviceArrayC),
                      A.ArrowDeviceArrayC.device_type.offset, A.ArrowDeviceArrayC.sync_event.offset]
