@@ -486,6 +486,26 @@ typedef struct qe_fused_spec {
   qe_agg_program inputs[QE_MAX_AGGS];
 } qe_fused_spec;
 
+/* Typing: an operation with an FLOAT64 operand (column or literal) is computed in fp64, its integral
+ * operand converted first (round to nearest even; an INT64 literal of a term against a FLOAT64
+ * column likewise); every other operation is int64 with narrow columns widened by value, wraps, and
+ * divides truncating toward zero, x / 0 being null (INT64_MIN / -1 wraps to INT64_MIN). A null
+ * operand or a null literal makes the value null with the type a valid one would have; a term whose
+ * side is null drops the row. An aggregate declared FLOAT64 (or AVG) over an integral program takes
+ * the program's int64 value converted to fp64. A program holds at most QE_MAX_TOKENS tokens once each
+ * such conversion is counted as one, and needs at most 4 stack entries.
+ * A plan is checked on the host before anything is launched; a refused plan changes no group:
+ *   QE_ERR_UNSUPPORTED  a column that is not INT64 / FLOAT64 / INT32 / DATE32 / UINT8 / BOOL (UTF8
+ *                       among the fused columns, read or not; UTF8 keys of a dictionary-keyed state
+ *                       are its own), more than QE_MAX_COLS columns or QE_MAX_TERMS terms, a program
+ *                       deeper than 4 or longer than QE_MAX_TOKENS after promotion, a literal that is
+ *                       neither INT64 nor FLOAT64;
+ *   QE_ERR_INVALID_ARG  a column slot outside [0, ncols) in a term, program, key or mask_col, a
+ *                       mask_col that is not BOOL, a comparison or token op outside its range, an
+ *                       empty program (but for COUNT_STAR), stack underflow, a program that leaves
+ *                       more than one value, an fp64 program for an aggregate declared integral (but
+ *                       for COUNT), columns of different lengths, a key column of another type than
+ *                       the state declares. */
 int qe_hashagg_update_fused(qe_hashagg* agg, const qe_column* cols, int32_t ncols,
                             const qe_fused_spec* spec);
 
