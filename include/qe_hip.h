@@ -280,6 +280,36 @@ int qe_take(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int3
  * single-workgroup path takes. Tests read the boundaries from here. */
 int qe_sort_layout(int32_t* tile_rows, int32_t* small_max);
 
+/* ORDER BY ... LIMIT k without the full sort. Keys, flags, types and the output column are those
+ * of qe_sort_indices (every fixed-width type, BOOL, short and long UTF8, nullable keys, DESC,
+ * NULLS_FIRST, up to QE_MAX_KEYS keys; out_indices INT32 without validity, capacity on entry >=
+ * min(k, n), length set). In every mode the result is exactly the first min(k, n) row indices of the
+ * stable order qe_sort_indices defines, in that order: ties on all keys by input row order, under
+ * DESC too; one permutation prefix, bit-identical from run to run.
+ * k < 0 and an unknown mode are QE_ERR_INVALID_ARG; k = 0 and n = 0 are legal and write nothing.
+ * QE_TOPK_SELECT: radix selection over the sort's key words, from the most significant 8-bit digit
+ * down. The first pass reads the key columns and writes only digit histograms; each digit step
+ * keeps the candidate rows at or below the threshold bin (a stable compaction, so the candidates
+ * stay in row order) until at most max(small_max, 2 k) remain (qe_sort_layout), and those are
+ * sorted by the stable sort. The host reads one histogram back per digit step and per key word the
+ * selection enters. Working memory: tile counters for n rows, and two (word, index) buffers of as
+ * many entries as survive the first digit step; released stream-ordered.
+ * QE_TOPK_SORT: the full sort, truncated (qe_sort_indices with limit = k).
+ * QE_TOPK_AUTO: SORT when n <= small_max or k >= n, SELECT when k <= n / 8.
+ * Lesser keys are examined only for rows that tie on the greater ones: a UTF8 key's max_len
+ * promise (1..7) is checked on the device for every row whose key word the call encodes, which for
+ * a key below the most significant word need not be every row. Keeping the promise on the rows
+ * the call does not examine is the caller's obligation. */
+#define QE_TOPK_AUTO 0
+#define QE_TOPK_SELECT 1
+#define QE_TOPK_SORT 2
+int qe_topk_indices(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, int32_t nkeys,
+                    int64_t k, int32_t mode, qe_column* out_indices);
+/* Measurement hook: the context's last qe_topk_indices call. stats[0] = path taken (0 the full
+ * sort, 1 selection), [1] = digit steps executed, [2] = candidate rows handed to the final sort,
+ * [3] = host read-backs. */
+int qe_topk_last_stats(qe_ctx* ctx, int64_t stats[4]);
+
 /* ---- equi-JOIN (build-defined; the reference's SQL has no JOIN) ------------------------------
  * A hash table is built once from the key column of one side (the build side) and probed by
  * batches of the other. The result is (probe row, build row) index pairs that qe_take /

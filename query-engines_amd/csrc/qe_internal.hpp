@@ -33,6 +33,7 @@ struct qe_ctx {
   void* sp_status = nullptr;     // per-tile counts of the register-resident select-project
   size_t sp_status_bytes = 0;
   uint32_t sp_epoch = 0;         // (epoch-tagged, so no memset per call; qe_selproj.hip)
+  int64_t topk_stats[4] = {};    // the last qe_topk_indices call (qe_topk_last_stats)
 };
 
 namespace qe {

@@ -15,6 +15,11 @@
 //                        LDS), stages the pairs in LDS in output order, writes each digit's rows
 //                        as one contiguous run
 //   n <= SORT_SMALL_MAX: k_sort_small, one workgroup, every word and digit in LDS, one launch.
+// qe_topk_indices
+//   The first k rows of the same stable order by radix selection from the most significant digit
+//   down (host rules: qe_topk_plan.hpp): k_topk_words (digit histograms; the first pass writes
+//   nothing else), per digit step k_topk_count / exclusive scan / k_topk_compact over a candidate
+//   list kept in row order, then k_sort_small_rows or the passes above over the candidates.
 // qe_take
 //   k_take: one row per lane, validity / BOOL words built per wave with __ballot; UTF8 through the
 //   (start, length) pairs, length scan and byte copy of qe_filter.hip.
@@ -24,6 +29,7 @@
 //   the count / scan / scatter passes over a caller's (word, index) buffers (qe_join.hip).
 #include "qe_internal.hpp"
 #include "qe_sort_key.hpp"
+#include "qe_topk_plan.hpp"
 
 namespace qe {
 
@@ -366,6 +372,257 @@ __global__ void __launch_bounds__(SORT_SMALL_THREADS) k_sort_small(SortDesc D, i
   for (int p = threadIdx.x; p < m_out; p += SORT_SMALL_THREADS) out[p] = s_idx[cur][p];
 }
 
+// k_sort_small over a row list (the top-k's final sort): the rows are the n entries of `rows` (row
+// indices below nrows, flag bit 31 ignored), not 0 .. n - 1, and rows that compare equal keep the
+// list's order. A kernel of its own, so that k_sort_small stays the kernel it was.
+__global__ void __launch_bounds__(SORT_SMALL_THREADS) k_sort_small_rows(SortDesc D, int32_t n, int32_t nrows,
+                                                                  const int32_t* __restrict__ rows, int32_t m_out,
+                                                                  int32_t* __restrict__ out, unsigned* __restrict__ err) {
+  __shared__ uint64_t s_word[2][SORT_SMALL_MAX];
+  __shared__ int32_t s_idx[2][SORT_SMALL_MAX];
+  constexpr int WAVES = SORT_SMALL_THREADS / 64;
+  __shared__ uint16_t s_wcnt[WAVES][256];
+  __shared__ uint32_t s_dstart[256];
+  __shared__ uint32_t s_wsum[4];
+  __shared__ uint64_t s_or[WAVES], s_and[WAVES];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  int cur = 0;
+  for (int p = threadIdx.x; p < n; p += SORT_SMALL_THREADS) s_idx[0][p] = rows[p] & 0x7FFFFFFF;
+  __syncthreads();
+  for (int k = 0; k < D.nwords; ++k) {
+    uint64_t o = 0, a = ~0ull;
+    for (int p = threadIdx.x; p < n; p += SORT_SMALL_THREADS) {
+      int32_t r = s_idx[cur][p];
+      if ((uint32_t)r >= (uint32_t)nrows) r = 0;
+      const uint64_t w = sort_word(D, r, k, err);
+      s_word[cur][p] = w;
+      o |= w;
+      a &= w;
+    }
+    for (int off = 32; off > 0; off >>= 1) {
+      o |= __shfl_xor(o, off);
+      a &= __shfl_xor(a, off);
+    }
+    if (lane == 0) {
+      s_or[wid] = o;
+      s_and[wid] = a;
+    }
+    __syncthreads();
+    o = 0;
+    a = ~0ull;
+#pragma unroll
+    for (int w = 0; w < WAVES; ++w) {
+      o |= s_or[w];
+      a &= s_and[w];
+    }
+    __syncthreads();
+    const uint64_t diff = o ^ a;  // bits that are not the same in every row (the same in every thread)
+    for (int g = 0; g < 8; ++g) {
+      if (((diff >> (8 * g)) & 255u) == 0) continue;
+      uint64_t w[SORT_SMALL_ITEMS];
+      int32_t ix[SORT_SMALL_ITEMS];
+      uint32_t dig[SORT_SMALL_ITEMS], pos[SORT_SMALL_ITEMS];
+#pragma unroll
+      for (int it = 0; it < SORT_SMALL_ITEMS; ++it) {
+        const int p = wid * (64 * SORT_SMALL_ITEMS) + it * 64 + lane;
+        const bool live = p < n;
+        w[it] = live ? s_word[cur][p] : ~0ull;
+        ix[it] = live ? s_idx[cur][p] : 0;
+        dig[it] = live ? (uint32_t)(w[it] >> (8 * g)) & 255u : 255u;
+      }
+      tile_rank<SORT_SMALL_THREADS, SORT_SMALL_ITEMS>(dig, pos, s_wcnt, s_dstart, s_wsum);
+#pragma unroll
+      for (int it = 0; it < SORT_SMALL_ITEMS; ++it) {
+        if (pos[it] < (uint32_t)SORT_SMALL_MAX) {
+          s_word[cur ^ 1][pos[it]] = w[it];
+          s_idx[cur ^ 1][pos[it]] = ix[it];
+        }
+      }
+      __syncthreads();
+      cur ^= 1;
+    }
+  }
+  for (int p = threadIdx.x; p < m_out; p += SORT_SMALL_THREADS) out[p] = s_idx[cur][p];
+}
+
+// ---- top-k: radix selection (qe_topk_plan.hpp holds the host's rules) ------------------------------
+// The candidate list: row indices in ascending row order, bit 31 set on a sure row. A tied row's
+// current key word lies beside it; a sure row's word is never read again. Before the first
+// compaction the list is implicit: every row, all tied.
+constexpr uint32_t TOPK_SURE = 0x80000000u;
+constexpr int TOPK_THREADS = 256;
+constexpr int TOPK_ITEMS = 16;
+constexpr int TOPK_TILE = TOPK_THREADS * TOPK_ITEMS;  // candidates per workgroup of a compaction
+static_assert(TOPK_TILE == SORT_TILE, "qe_sort_layout reports one tile size");
+
+// Key words of list entries, and the 8 digit histograms of the rows it encodes.
+//   TW_ALL  : the implicit list, rows 0 .. m - 1; nothing but the histograms is written
+//   TW_TIED : word k of the tied entries of `cand` -> words[i]
+//   TW_SORT : word k of every entry of `cand` -> words[i]; `strip`: the flag bits leave `cand` (the
+//             final sort's first word: from here on the list is the sort's permutation)
+enum { TW_ALL = 0, TW_TIED = 1, TW_SORT = 2 };
+template <int MODE>
+__global__ void __launch_bounds__(ENC_THREADS) k_topk_words(SortDesc D, int64_t k, int64_t nrows, int64_t m,
+                                                             int32_t* __restrict__ cand, uint64_t* __restrict__ words,
+                                                             int strip, uint32_t* __restrict__ hist,
+                                                             unsigned* __restrict__ err) {
+  __shared__ uint32_t h[8 * 256];
+  for (int j = threadIdx.x; j < 8 * 256; j += ENC_THREADS) h[j] = 0;
+  __syncthreads();
+  for (int64_t i = blockIdx.x * (int64_t)ENC_THREADS + threadIdx.x; i < m; i += (int64_t)gridDim.x * ENC_THREADS) {
+    int64_t r = i;
+    if (MODE != TW_ALL) {
+      const uint32_t c = (uint32_t)cand[i];
+      if (MODE == TW_TIED && (c & TOPK_SURE)) continue;
+      r = (int64_t)(c & ~TOPK_SURE);
+      if (MODE == TW_SORT && strip) cand[i] = (int32_t)r;
+    }
+    if ((uint64_t)r >= (uint64_t)nrows) r = 0;  // (a candidate never is)
+    const uint64_t w = sort_word(D, r, k, err);
+    if (MODE != TW_ALL) words[i] = w;
+#pragma unroll
+    for (int g = 0; g < 8; ++g) hist_add(h + 256 * g, (uint32_t)(w >> (8 * g)) & 255u);
+  }
+  __syncthreads();
+  for (int j = threadIdx.x; j < 8 * 256; j += ENC_THREADS)
+    if (h[j]) atomicAdd(&hist[j], h[j]);
+}
+
+struct TopkStep {
+  int64_t k;         // the key word in play
+  int32_t shift;     // 8 x its digit in play
+  uint32_t bin;      // the threshold bin: a tied row with a smaller digit becomes sure, a larger one leaves
+  int32_t cut_only;  // no digit is in play: every tied row stays tied (the cut after the last digit)
+  int32_t pad;
+  int64_t cut;       // the tied rows that stay: the first `cut` in row order
+};
+
+// What becomes of candidate i under step S: 0 it leaves, 1 sure, 2 tied. *w = its word when tied before.
+template <bool ALL>
+__device__ __forceinline__ uint32_t topk_class(const SortDesc& D, const TopkStep& S, int64_t i,
+                                               const int32_t* __restrict__ cand, const uint64_t* __restrict__ words,
+                                               int32_t* row, uint64_t* w, unsigned* err) {
+  if (ALL) {
+    *row = (int32_t)i;
+    *w = sort_word(D, i, S.k, err);
+  } else {
+    const uint32_t c = (uint32_t)cand[i];
+    *row = (int32_t)(c & ~TOPK_SURE);
+    if (c & TOPK_SURE) return 1u;
+    *w = words[i];
+  }
+  if (S.cut_only) return 2u;
+  const uint32_t d = (uint32_t)(*w >> S.shift) & 255u;
+  return d < S.bin ? 1u : d == S.bin ? 2u : 0u;
+}
+
+// counts[tile] = candidates of the tile that stay as sure rows, counts[ntiles + tile] = as tied rows
+// (before the cut).
+template <bool ALL>
+__global__ void __launch_bounds__(TOPK_THREADS) k_topk_count(SortDesc D, TopkStep S, int64_t m,
+                                                              const int32_t* __restrict__ cand,
+                                                              const uint64_t* __restrict__ words, int64_t ntiles,
+                                                              int64_t* __restrict__ counts, unsigned* __restrict__ err) {
+  __shared__ uint32_t s_cnt[2];
+  if (threadIdx.x < 2) s_cnt[threadIdx.x] = 0;
+  __syncthreads();
+  const int64_t t0 = (int64_t)blockIdx.x * TOPK_TILE;
+  uint32_t ns = 0, nt = 0;
+  for (int it = 0; it < TOPK_ITEMS; ++it) {
+    const int64_t i = t0 + it * TOPK_THREADS + threadIdx.x;
+    uint32_t cls = 0;
+    if (i < m) {
+      int32_t row;
+      uint64_t w = 0;
+      cls = topk_class<ALL>(D, S, i, cand, words, &row, &w, err);
+    }
+    ns += (uint32_t)__popcll(__ballot(cls == 1u));
+    nt += (uint32_t)__popcll(__ballot(cls == 2u));
+  }
+  if ((threadIdx.x & 63) == 0) {
+    atomicAdd(&s_cnt[0], ns);
+    atomicAdd(&s_cnt[1], nt);
+  }
+  __syncthreads();
+  if (threadIdx.x < 2) counts[(int64_t)threadIdx.x * ntiles + blockIdx.x] = s_cnt[threadIdx.x];
+}
+
+// The stable compaction of one tile. Candidate p of the tile is item `it` of lane `lane` of wave
+// `wid` with p = wid * 64 * ITEMS + it * 64 + lane, so a wave owns a contiguous run and ranks it by
+// ballots alone. offs = the exclusive scan of k_topk_count's counts: a staying row goes to
+// (sure rows before it) + min(tied rows before it, cut), and a tied row stays iff fewer than `cut`
+// tied rows precede it, which keeps the list in ascending row order. hist (may be NULL): the 8 digit
+// histograms of the rows that stay tied, for the next step's pick.
+template <bool ALL>
+__global__ void __launch_bounds__(TOPK_THREADS) k_topk_compact(SortDesc D, TopkStep S, int64_t m,
+                                                                const int32_t* __restrict__ cand,
+                                                                const uint64_t* __restrict__ words, int64_t ntiles,
+                                                                const int64_t* __restrict__ offs, int64_t mout,
+                                                                int32_t* __restrict__ cand_out,
+                                                                uint64_t* __restrict__ words_out,
+                                                                uint32_t* __restrict__ hist, unsigned* __restrict__ err) {
+  constexpr int WAVES = TOPK_THREADS / 64;
+  __shared__ uint32_t h[8 * 256];
+  __shared__ uint32_t s_ws[WAVES], s_wt[WAVES];
+  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
+  const uint64_t lt = (1ull << lane) - 1;
+  if (hist)
+    for (int j = threadIdx.x; j < 8 * 256; j += TOPK_THREADS) h[j] = 0;
+  const int64_t t0 = (int64_t)blockIdx.x * TOPK_TILE + wid * (64 * TOPK_ITEMS);
+  uint64_t w[TOPK_ITEMS];
+  int32_t row[TOPK_ITEMS];
+  uint32_t cls = 0, ns = 0, nt = 0;  // 2 class bits per item; this wave's totals
+#pragma unroll
+  for (int it = 0; it < TOPK_ITEMS; ++it) {
+    const int64_t i = t0 + it * 64 + lane;
+    uint32_t c = 0;
+    w[it] = 0;
+    row[it] = 0;
+    if (i < m) c = topk_class<ALL>(D, S, i, cand, words, &row[it], &w[it], err);
+    cls |= c << (2 * it);
+    ns += (uint32_t)__popcll(__ballot(c == 1u));
+    nt += (uint32_t)__popcll(__ballot(c == 2u));
+  }
+  if (lane == 0) {
+    s_ws[wid] = ns;
+    s_wt[wid] = nt;
+  }
+  __syncthreads();
+  // rows that stay before this wave's first: the earlier tiles' (from the scan) and the earlier waves'
+  int64_t sb = offs[blockIdx.x], tb = offs[ntiles + blockIdx.x] - offs[ntiles];
+#pragma unroll
+  for (int v = 0; v < WAVES; ++v) {
+    if (v < wid) {
+      sb += s_ws[v];
+      tb += s_wt[v];
+    }
+  }
+#pragma unroll
+  for (int it = 0; it < TOPK_ITEMS; ++it) {
+    const uint32_t c = (cls >> (2 * it)) & 3u;
+    const uint64_t ms = __ballot(c == 1u), mt = __ballot(c == 2u);
+    const int64_t s_before = sb + __popcll(ms & lt), t_before = tb + __popcll(mt & lt);
+    if (c == 1u || (c == 2u && t_before < S.cut)) {
+      const int64_t o = s_before + (t_before < S.cut ? t_before : S.cut);
+      if ((uint64_t)o < (uint64_t)mout) {
+        cand_out[o] = (int32_t)((uint32_t)row[it] | (c == 1u ? TOPK_SURE : 0u));
+        if (c == 2u) words_out[o] = w[it];
+      }
+      if (c == 2u && hist) {
+#pragma unroll
+        for (int g = 0; g < 8; ++g) hist_add(h + 256 * g, (uint32_t)(w[it] >> (8 * g)) & 255u);
+      }
+    }
+    sb += __popcll(ms);
+    tb += __popcll(mt);
+  }
+  if (hist) {
+    __syncthreads();
+    for (int j = threadIdx.x; j < 8 * 256; j += TOPK_THREADS)
+      if (h[j]) atomicAdd(&hist[j], h[j]);
+  }
+}
+
 // ---- qe_take -----------------------------------------------------------------------------------
 constexpr int TAKE_MAX_COLS = 8;
 enum { TK_UTF8 = 0, TK_BOOL = -1 };
@@ -476,65 +733,92 @@ int sort_pairs(qe_ctx* ctx, uint64_t* const words[2], int32_t* const idx[2], int
   return QE_OK;
 }
 
-}  // namespace qe
-
-using namespace qe;
-
-extern "C" {
-
-int qe_sort_layout(int32_t* tile_rows, int32_t* small_max) {
-  if (tile_rows) *tile_rows = SORT_TILE;
-  if (small_max) *small_max = SORT_SMALL_MAX;
+// ---- host side of qe_sort_indices / qe_topk_indices -------------------------------------------------
+// Argument rules of both calls (`who`: the one that reports) up to the output column's type; *n_out =
+// the row count.
+static int sort_check_args(const char* who, const qe_column* keys, const int32_t* flags, int32_t nkeys, const qe_column* out_indices,
+                           int64_t* n_out) {
+  QE_CHECK(nkeys >= 1 && nkeys <= QE_MAX_KEYS, QE_ERR_INVALID_ARG, "%s: 1..%d keys, got %d", who, QE_MAX_KEYS, nkeys);
+  QE_CHECK(keys && flags && out_indices, QE_ERR_INVALID_ARG, "%s: null keys, flags or output", who);
+  const int64_t n = keys[0].length;
+  QE_CHECK(n >= 0 && n < ((int64_t)1 << 31), QE_ERR_INVALID_ARG, "%s: %lld rows (at most 2^31 - 1)", who, (long long)n);
+  for (int q = 0; q < nkeys; ++q) {
+    const qe_column& c = keys[q];
+    QE_CHECK(c.length == n, QE_ERR_INVALID_ARG, "%s: key %d has %lld rows, key 0 %lld", who, q, (long long)c.length,
+             (long long)n);
+    QE_CHECK((flags[q] & ~(QE_SORT_DESC | QE_SORT_NULLS_FIRST)) == 0, QE_ERR_INVALID_ARG,
+             "%s: key %d has unknown flag bits 0x%x", who, q, flags[q]);
+    QE_CHECK(sort_value_bits(c.type) > 0 || c.type == QE_TYPE_UTF8, QE_ERR_UNSUPPORTED, "%s: key %d type %d", who, q, c.type);
+    QE_CHECK(c.values || n == 0, QE_ERR_INVALID_ARG, "%s: key %d has no values", who, q);
+    QE_CHECK(c.type != QE_TYPE_UTF8 || c.offsets || n == 0, QE_ERR_INVALID_ARG, "%s: UTF8 key %d needs offsets", who, q);
+  }
+  QE_CHECK(out_indices->type == QE_TYPE_INT32 && !out_indices->validity, QE_ERR_INVALID_ARG,
+           "%s: the indices column must be INT32 without validity", who);
+  *n_out = n;
   return QE_OK;
 }
 
-int qe_sort_indices(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, int32_t nkeys, int64_t limit,
-                    qe_column* out_indices) {
-  QE_TRY(ctx_enter(ctx));
-  QE_CHECK(nkeys >= 1 && nkeys <= QE_MAX_KEYS, QE_ERR_INVALID_ARG, "sort: 1..%d keys, got %d", QE_MAX_KEYS, nkeys);
-  QE_CHECK(keys && flags && out_indices, QE_ERR_INVALID_ARG, "sort: null keys, flags or output");
-  const int64_t n = keys[0].length;
-  QE_CHECK(n >= 0 && n < ((int64_t)1 << 31), QE_ERR_INVALID_ARG, "sort: %lld rows (at most 2^31 - 1)", (long long)n);
-  for (int q = 0; q < nkeys; ++q) {
-    const qe_column& c = keys[q];
-    QE_CHECK(c.length == n, QE_ERR_INVALID_ARG, "sort: key %d has %lld rows, key 0 %lld", q, (long long)c.length,
-             (long long)n);
-    QE_CHECK((flags[q] & ~(QE_SORT_DESC | QE_SORT_NULLS_FIRST)) == 0, QE_ERR_INVALID_ARG,
-             "sort: key %d has unknown flag bits 0x%x", q, flags[q]);
-    QE_CHECK(sort_value_bits(c.type) > 0 || c.type == QE_TYPE_UTF8, QE_ERR_UNSUPPORTED, "sort: key %d type %d", q, c.type);
-    QE_CHECK(c.values || n == 0, QE_ERR_INVALID_ARG, "sort: key %d has no values", q);
-    QE_CHECK(c.type != QE_TYPE_UTF8 || c.offsets || n == 0, QE_ERR_INVALID_ARG, "sort: UTF8 key %d needs offsets", q);
-  }
-  QE_CHECK(out_indices->type == QE_TYPE_INT32 && !out_indices->validity, QE_ERR_INVALID_ARG,
-           "sort: the indices column must be INT32 without validity");
-  const int64_t m = limit < 0 ? n : std::min(limit, n);
-  QE_CHECK(out_indices->length >= m, QE_ERR_CAPACITY, "sort: the indices column holds %lld rows, need %lld",
+// The output column holds the m result rows; its length is set.
+static int sort_check_out(const char* who, qe_column* out_indices, int64_t m) {
+  QE_CHECK(out_indices->length >= m, QE_ERR_CAPACITY, "%s: the indices column holds %lld rows, need %lld", who,
            (long long)out_indices->length, (long long)m);
-  QE_CHECK(out_indices->values || m == 0, QE_ERR_INVALID_ARG, "sort: the indices column has no values");
+  QE_CHECK(out_indices->values || m == 0, QE_ERR_INVALID_ARG, "%s: the indices column has no values", who);
   out_indices->length = m;
-  if (m == 0) return QE_OK;
+  return QE_OK;
+}
 
-  // working memory: [err word + UTF8 lengths | histograms | 2 x words | 2 x indices | counts | offsets]
-  const bool small = n <= SORT_SMALL_MAX;
-  const int64_t ntiles = (int64_t)div_up((uint64_t)n, SORT_TILE);
-  const size_t head = 256, hist_b = 8 * 256 * 4;
-  const size_t words_b = small ? 0 : align256((size_t)n * 8), idx_b = small ? 0 : align256((size_t)n * 4);
-  const size_t cnt_b = small ? 0 : align256((size_t)(256 * ntiles + 1) * 8);
-  DevBlock blk(ctx);
-  QE_TRY(dev_alloc(ctx, head + hist_b + 2 * words_b + 2 * idx_b + 2 * cnt_b, &blk.p));
+// One call's working memory, carved from one block:
+// [err word + UTF8 lengths | histograms | 2 x words | 2 x indices | counts | offsets]
+constexpr size_t SORT_HEAD = 256, SORT_HIST_B = 8 * 256 * 4;
+struct SortMem {
+  const char* who;  // the entry point, for its error messages
+  char* base;  // head[0]: error word; head[4 + 4 q]: longest value of UTF8 key q
+  unsigned* err;
+  uint32_t* hist;
+  uint64_t* words[2];
+  int32_t* idx[2];
+  int64_t *counts, *offs;
+  void* hp;  // pinned: the head and the histograms as read back
+  const unsigned* h_err;
+  const uint32_t* h_hist;
+  int64_t readbacks = 0;
+};
+
+// rows: entries of each pair buffer; cnt: entries of each of the two counter arrays (0: none).
+static int sort_mem(qe_ctx* ctx, DevBlock& blk, int64_t rows, int64_t cnt, SortMem* M) {
+  const size_t words_b = rows ? align256((size_t)rows * 8) : 0, idx_b = rows ? align256((size_t)rows * 4) : 0;
+  const size_t cnt_b = cnt ? align256((size_t)cnt * 8) : 0;
+  QE_TRY(dev_alloc(ctx, SORT_HEAD + SORT_HIST_B + 2 * words_b + 2 * idx_b + 2 * cnt_b, &blk.p));
   char* base = (char*)blk.p;
-  unsigned* d_err = (unsigned*)base;  // head[0]: error word; head[4 + 4 q]: longest value of UTF8 key q
-  uint32_t* d_hist = (uint32_t*)(base + head);
-  uint64_t* d_words[2] = {(uint64_t*)(base + head + hist_b), (uint64_t*)(base + head + hist_b + words_b)};
-  int32_t* d_idx[2] = {(int32_t*)(base + head + hist_b + 2 * words_b), (int32_t*)(base + head + hist_b + 2 * words_b + idx_b)};
-  int64_t* d_counts = (int64_t*)(base + head + hist_b + 2 * words_b + 2 * idx_b);
-  int64_t* d_offs = (int64_t*)((char*)d_counts + cnt_b);
-  QE_HIP(hipMemsetAsync(base, 0, head, ctx->stream));
-  void* hp;
-  QE_TRY(ctx_pinned(ctx, head + hist_b, &hp));
-  const unsigned* h_err = (const unsigned*)hp;
-  const uint32_t* h_hist = (const uint32_t*)((char*)hp + head);
+  M->base = base;
+  M->err = (unsigned*)base;
+  M->hist = (uint32_t*)(base + SORT_HEAD);
+  char* p = base + SORT_HEAD + SORT_HIST_B;
+  M->words[0] = (uint64_t*)p;
+  M->words[1] = (uint64_t*)(p + words_b);
+  M->idx[0] = (int32_t*)(p + 2 * words_b);
+  M->idx[1] = (int32_t*)(p + 2 * words_b + idx_b);
+  M->counts = (int64_t*)(p + 2 * words_b + 2 * idx_b);
+  M->offs = (int64_t*)((char*)M->counts + cnt_b);
+  QE_HIP(hipMemsetAsync(base, 0, SORT_HEAD, ctx->stream));
+  QE_TRY(ctx_pinned(ctx, SORT_HEAD + SORT_HIST_B, &M->hp));
+  M->h_err = (const unsigned*)M->hp;
+  M->h_hist = (const uint32_t*)((char*)M->hp + SORT_HEAD);
+  return QE_OK;
+}
 
+// The head and the histograms come back; a broken short-UTF8 promise fails the call here.
+static int sort_read_back(qe_ctx* ctx, SortMem& M, size_t bytes) {
+  QE_HIP(hipMemcpyAsync(M.hp, M.base, bytes, hipMemcpyDeviceToHost, ctx->stream));
+  QE_TRY(ctx_sync(ctx));
+  ++M.readbacks;
+  QE_CHECK(M.h_err[0] == 0, QE_ERR_INVALID_ARG, "%s: a UTF8 key value is longer than the column's max_len", M.who);
+  return QE_OK;
+}
+
+// The key layout of a call. *promised: a UTF8 key relies on max_len (the device checks the bound).
+static int sort_build_desc(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, int32_t nkeys, int64_t n, SortMem& M,
+                           SortDesc* D_out, bool* promised_out) {
   // UTF8 keys without a bound of at most 7 bytes: the longest value, one reduction each, one read-back
   int64_t longest[QE_MAX_KEYS] = {};
   bool promised = false, reduced = false;
@@ -547,16 +831,17 @@ int qe_sort_indices(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, in
     }
     const int grid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)n, 256), (int64_t)ctx->num_cus * 8);
     hipLaunchKernelGGL(k_utf8_max_len, dim3(grid), dim3(256), 0, ctx->stream, keys[q].offsets, n,
-                       (int32_t*)base + 4 + 4 * q);
+                       (int32_t*)M.base + 4 + 4 * q);
     QE_TRY(launch_check("k_utf8_max_len"));
     reduced = true;
   }
   if (reduced) {
-    QE_HIP(hipMemcpyAsync(hp, base, head, hipMemcpyDeviceToHost, ctx->stream));
+    QE_HIP(hipMemcpyAsync(M.hp, M.base, SORT_HEAD, hipMemcpyDeviceToHost, ctx->stream));
     QE_TRY(ctx_sync(ctx));
+    ++M.readbacks;
     for (int q = 0; q < nkeys; ++q)
       if (keys[q].type == QE_TYPE_UTF8 && !(keys[q].max_len >= 1 && keys[q].max_len <= 7))
-        longest[q] = ((const int32_t*)hp)[4 + 4 * q];
+        longest[q] = ((const int32_t*)M.hp)[4 + 4 * q];
   }
 
   // key layout, from the least significant bit: the last key first
@@ -592,53 +877,267 @@ int qe_sort_indices(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, in
     if (c.validity) K.lo_n = lo++;
   }
   const int64_t nwords = (lo + 63) / 64;
-  QE_CHECK(nwords <= SORT_MAX_WORDS, QE_ERR_UNSUPPORTED, "sort: the keys take %lld bytes per row (at most %lld)",
+  QE_CHECK(nwords <= SORT_MAX_WORDS, QE_ERR_UNSUPPORTED, "%s: the keys take %lld bytes per row (at most %lld)", M.who,
            (long long)nwords * 8, (long long)SORT_MAX_WORDS * 8);
   D.nwords = (int32_t)nwords;
+  *D_out = D;
+  *promised_out = promised;
+  return QE_OK;
+}
 
-  if (small) {
-    hipLaunchKernelGGL(k_sort_small, dim3(1), dim3(SORT_SMALL_THREADS), 0, ctx->stream, D, (int32_t)n, (int32_t)m,
-                       (int32_t*)out_indices->values, d_err);
-    QE_TRY(launch_check("k_sort_small"));
-    if (promised) {  // (nothing else of this path needs the host)
-      QE_HIP(hipMemcpyAsync(hp, base, 4, hipMemcpyDeviceToHost, ctx->stream));
-      QE_TRY(ctx_sync(ctx));
-      QE_CHECK(h_err[0] == 0, QE_ERR_INVALID_ARG, "sort: a UTF8 key value is longer than the column's max_len");
+// The multi-workgroup sort of m rows of a column of nrows: per word, the encode through the current
+// permutation and the passes of its varying digits. list: the rows are the m entries of M.idx[cur]
+// (a top-k candidate list, flag bits included); otherwise rows 0 .. m - 1 (m == nrows). *cur_out =
+// the index buffer that holds the order.
+static int sort_multi(qe_ctx* ctx, const SortDesc& D, int64_t nrows, int64_t m, bool list, SortMem& M, int cur,
+                      int* cur_out) {
+  const int64_t ntiles = (int64_t)div_up((uint64_t)m, SORT_TILE);
+  const int egrid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)m, ENC_THREADS), (int64_t)ctx->num_cus * 8);
+  for (int64_t k = 0; k < D.nwords; ++k) {
+    QE_HIP(hipMemsetAsync(M.hist, 0, SORT_HIST_B, ctx->stream));
+    if (list) {
+      hipLaunchKernelGGL(k_topk_words<TW_SORT>, dim3(egrid), dim3(ENC_THREADS), 0, ctx->stream, D, k, nrows, m, M.idx[cur],
+                         M.words[cur], k == 0 ? 1 : 0, M.hist, M.err);
+      QE_TRY(launch_check("k_topk_words"));
+    } else {
+      hipLaunchKernelGGL(k_sort_encode, dim3(egrid), dim3(ENC_THREADS), 0, ctx->stream, D, k, m,
+                         k == 0 ? (const int32_t*)nullptr : (const int32_t*)M.idx[cur], M.words[cur],
+                         k == 0 ? M.idx[cur] : (int32_t*)nullptr, M.hist, M.err);
+      QE_TRY(launch_check("k_sort_encode"));
     }
-    return QE_OK;
-  }
-
-  const int egrid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)n, ENC_THREADS), (int64_t)ctx->num_cus * 8);
-  int cur = 0;
-  for (int64_t k = 0; k < nwords; ++k) {
-    QE_HIP(hipMemsetAsync(d_hist, 0, hist_b, ctx->stream));
-    hipLaunchKernelGGL(k_sort_encode, dim3(egrid), dim3(ENC_THREADS), 0, ctx->stream, D, k, n,
-                       k == 0 ? (const int32_t*)nullptr : (const int32_t*)d_idx[cur], d_words[cur],
-                       k == 0 ? d_idx[cur] : (int32_t*)nullptr, d_hist, d_err);
-    QE_TRY(launch_check("k_sort_encode"));
-    QE_HIP(hipMemcpyAsync(hp, base, head + hist_b, hipMemcpyDeviceToHost, ctx->stream));
-    QE_TRY(ctx_sync(ctx));
-    QE_CHECK(h_err[0] == 0, QE_ERR_INVALID_ARG, "sort: a UTF8 key value is longer than the column's max_len");
+    QE_TRY(sort_read_back(ctx, M, SORT_HEAD + SORT_HIST_B));
     int digits[8], nd = 0;
     for (int g = 0; g < 8; ++g) {
       bool constant = false;
-      for (int v = 0; v < 256; ++v) constant |= h_hist[256 * g + v] == (uint32_t)n;
+      for (int v = 0; v < 256; ++v) constant |= M.h_hist[256 * g + v] == (uint32_t)m;
       if (!constant) digits[nd++] = g;
     }
     for (int j = 0; j < nd; ++j) {
       const int shift = 8 * digits[j];
-      hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, d_words[cur], n, shift,
-                         ntiles, d_counts);
+      hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, M.words[cur], m, shift,
+                         ntiles, M.counts);
       QE_TRY(launch_check("k_sort_count"));
-      QE_TRY(exclusive_scan_i64(ctx, d_counts, d_offs, 256 * ntiles));
-      hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, d_words[cur],
-                         d_idx[cur], j + 1 < nd ? d_words[cur ^ 1] : (uint64_t*)nullptr, d_idx[cur ^ 1], n, shift, ntiles,
-                         d_offs);
+      QE_TRY(exclusive_scan_i64(ctx, M.counts, M.offs, 256 * ntiles));
+      hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, M.words[cur],
+                         M.idx[cur], j + 1 < nd ? M.words[cur ^ 1] : (uint64_t*)nullptr, M.idx[cur ^ 1], m, shift, ntiles,
+                         M.offs);
       QE_TRY(launch_check("k_sort_scatter"));
       cur ^= 1;
     }
   }
-  QE_HIP(hipMemcpyAsync(out_indices->values, d_idx[cur], (size_t)m * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  *cur_out = cur;
+  return QE_OK;
+}
+
+// qe_sort_indices (and qe_topk_indices' QE_TOPK_SORT, which reports as `who`); *readbacks (may be
+// NULL) = the host read-backs of the call.
+static int sort_impl(qe_ctx* ctx, const char* who, const qe_column* keys, const int32_t* flags, int32_t nkeys,
+                     int64_t limit, qe_column* out_indices, int64_t* readbacks) {
+  int64_t n;
+  QE_TRY(sort_check_args(who, keys, flags, nkeys, out_indices, &n));
+  const int64_t m = limit < 0 ? n : std::min(limit, n);
+  QE_TRY(sort_check_out(who, out_indices, m));
+  if (m == 0) return QE_OK;
+
+  const bool small = n <= SORT_SMALL_MAX;
+  const int64_t ntiles = (int64_t)div_up((uint64_t)n, SORT_TILE);
+  DevBlock blk(ctx);
+  SortMem M;
+  M.who = who;
+  QE_TRY(sort_mem(ctx, blk, small ? 0 : n, small ? 0 : 256 * ntiles + 1, &M));
+  SortDesc D;
+  bool promised;
+  int st = sort_build_desc(ctx, keys, flags, nkeys, n, M, &D, &promised);
+  if (st == QE_OK && small) {
+    hipLaunchKernelGGL(k_sort_small, dim3(1), dim3(SORT_SMALL_THREADS), 0, ctx->stream, D, (int32_t)n, (int32_t)m,
+                       (int32_t*)out_indices->values, M.err);
+    st = launch_check("k_sort_small");
+    if (st == QE_OK && promised) st = sort_read_back(ctx, M, 4);  // (nothing else of this path needs the host)
+  } else if (st == QE_OK) {
+    int cur = 0;
+    st = sort_multi(ctx, D, n, n, false, M, 0, &cur);
+    if (st == QE_OK && hipMemcpyAsync(out_indices->values, M.idx[cur], (size_t)m * 4, hipMemcpyDeviceToDevice, ctx->stream) != hipSuccess)
+      st = fail(QE_ERR_DEVICE, "%s: copying the indices failed", who);
+  }
+  if (readbacks) *readbacks = M.readbacks;
+  return st;
+}
+
+// The top-k's two (word, index) candidate buffers of `rows` entries each, in a block of their own:
+// they are sized once the first pick has bounded the candidates, after the block of sort_mem.
+static int topk_mem_pairs(qe_ctx* ctx, DevBlock& blk, int64_t rows, SortMem* M) {
+  const size_t words_b = align256((size_t)rows * 8), idx_b = align256((size_t)rows * 4);
+  QE_TRY(dev_alloc(ctx, 2 * words_b + 2 * idx_b, &blk.p));
+  char* p = (char*)blk.p;
+  M->words[0] = (uint64_t*)p;
+  M->words[1] = (uint64_t*)(p + words_b);
+  M->idx[0] = (int32_t*)(p + 2 * words_b);
+  M->idx[1] = (int32_t*)(p + 2 * words_b + idx_b);
+  return QE_OK;
+}
+
+// The 8 digit histograms of word kw over the tied rows of the `cand` candidates in M.idx[cur] /
+// M.words[cur] (implicit: over all n rows, and nothing else is written), read back.
+static int topk_histogram(qe_ctx* ctx, const SortDesc& D, int64_t kw, int64_t n, bool implicit, int64_t cand, SortMem& M,
+                          int cur) {
+  const int egrid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)cand, ENC_THREADS), (int64_t)ctx->num_cus * 8);
+  QE_HIP(hipMemsetAsync(M.hist, 0, SORT_HIST_B, ctx->stream));
+  if (implicit)
+    hipLaunchKernelGGL(k_topk_words<TW_ALL>, dim3(egrid), dim3(ENC_THREADS), 0, ctx->stream, D, kw, n, n, (int32_t*)nullptr,
+                       (uint64_t*)nullptr, 0, M.hist, M.err);
+  else
+    hipLaunchKernelGGL(k_topk_words<TW_TIED>, dim3(egrid), dim3(ENC_THREADS), 0, ctx->stream, D, kw, n, cand, M.idx[cur],
+                       M.words[cur], 0, M.hist, M.err);
+  QE_TRY(launch_check("k_topk_words"));
+  return sort_read_back(ctx, M, SORT_HEAD + SORT_HIST_B);
+}
+
+// One digit step (or the final cut) of the selection: the m candidates of M.idx[cur] / M.words[cur]
+// (implicit: rows 0 .. m - 1) that stay under S go to the other buffers (implicit: buffers 0), mout
+// of them. want_hist: M.hist receives the histograms of the rows that stay tied.
+static int topk_compact(qe_ctx* ctx, const SortDesc& D, const TopkStep& S, bool implicit, int64_t m, int64_t mout,
+                        SortMem& M, int cur, bool want_hist) {
+  const int64_t ntiles = (int64_t)div_up((uint64_t)m, TOPK_TILE);
+  const int out = implicit ? 0 : cur ^ 1;
+  uint32_t* hist = want_hist ? M.hist : nullptr;
+  if (want_hist) QE_HIP(hipMemsetAsync(M.hist, 0, SORT_HIST_B, ctx->stream));
+  if (implicit)
+    hipLaunchKernelGGL(k_topk_count<true>, dim3((unsigned)ntiles), dim3(TOPK_THREADS), 0, ctx->stream, D, S, m,
+                       (const int32_t*)nullptr, (const uint64_t*)nullptr, ntiles, M.counts, M.err);
+  else
+    hipLaunchKernelGGL(k_topk_count<false>, dim3((unsigned)ntiles), dim3(TOPK_THREADS), 0, ctx->stream, D, S, m,
+                       (const int32_t*)M.idx[cur], (const uint64_t*)M.words[cur], ntiles, M.counts, M.err);
+  QE_TRY(launch_check("k_topk_count"));
+  QE_TRY(exclusive_scan_i64(ctx, M.counts, M.offs, 2 * ntiles));
+  if (implicit)
+    hipLaunchKernelGGL(k_topk_compact<true>, dim3((unsigned)ntiles), dim3(TOPK_THREADS), 0, ctx->stream, D, S, m,
+                       (const int32_t*)nullptr, (const uint64_t*)nullptr, ntiles, (const int64_t*)M.offs, mout, M.idx[out],
+                       M.words[out], hist, M.err);
+  else
+    hipLaunchKernelGGL(k_topk_compact<false>, dim3((unsigned)ntiles), dim3(TOPK_THREADS), 0, ctx->stream, D, S, m,
+                       (const int32_t*)M.idx[cur], (const uint64_t*)M.words[cur], ntiles, (const int64_t*)M.offs, mout,
+                       M.idx[out], M.words[out], hist, M.err);
+  return launch_check("k_topk_compact");
+}
+
+// qe_topk_indices in selection mode: n > 0 rows, the first m = min(k, n) > 0 of the order. Everything
+// here is a function of m, never of the caller's k (which may be INT64_MAX). stats[1], stats[2] =
+// the digit steps and the candidates handed to the final sort; M.readbacks counts the read-backs.
+static int topk_select(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, int32_t nkeys, int64_t n, int64_t m,
+                       int32_t* out, SortMem& M, int64_t* stats) {
+  // working memory: a block of [head | histograms | tile counters] now; the candidate buffers in a
+  // second block once the first pick says how many rows survive (both released stream-ordered)
+  const int64_t fmax = std::min(n, std::max<int64_t>(SORT_SMALL_MAX, (int64_t)QE_TOPK_STOP_FACTOR * m));
+  const int64_t cnt = n <= SORT_SMALL_MAX ? 0
+                                          : std::max<int64_t>(2 * (int64_t)div_up((uint64_t)n, TOPK_TILE) + 1,
+                                                              256 * (int64_t)div_up((uint64_t)fmax, SORT_TILE) + 1);
+  DevBlock blk(ctx), pairs(ctx);
+  QE_TRY(sort_mem(ctx, blk, 0, cnt, &M));
+  SortDesc D;
+  bool promised;
+  QE_TRY(sort_build_desc(ctx, keys, flags, nkeys, n, M, &D, &promised));
+
+  TopkNeed C{m, 0, n};
+  bool implicit = true, have_hist = false;
+  int cur = 0;
+  int64_t kw = D.nwords - 1;
+  while (!topk_stop(C.candidates(), m, SORT_SMALL_MAX)) {
+    const int64_t before = C.candidates();
+    // the highest digit, of this word or of a lower one, on which the tied rows differ
+    int32_t g = -1;
+    for (; kw >= 0; --kw, have_hist = false) {
+      if (!have_hist) QE_TRY(topk_histogram(ctx, D, kw, n, implicit, before, M, cur));
+      have_hist = true;
+      g = topk_top_digit(M.h_hist, C.tied);
+      if (g >= 0) break;
+    }
+    TopkStep S{};
+    S.cut = INT64_MAX;
+    if (g >= 0) {
+      const TopkPick P = topk_pick_bin(M.h_hist + 256 * g, C.need());
+      QE_CHECK(P.bin >= 0, QE_ERR_DEVICE, "topk: the digit histogram holds fewer rows than the selection needs");
+      S.k = kw;
+      S.shift = 8 * g;
+      S.bin = (uint32_t)P.bin;
+      C.take(P);
+      ++stats[1];
+    } else {  // every digit of every word is spent: the tied rows are equal, the first need() of them stay
+      S.cut_only = 1;
+      S.cut = C.need();
+      C.cut();
+    }
+    have_hist = g >= 0 && !topk_stop(C.candidates(), m, SORT_SMALL_MAX);  // another step follows: it needs histograms
+    if (implicit) QE_TRY(topk_mem_pairs(ctx, pairs, C.candidates(), &M));
+    QE_TRY(topk_compact(ctx, D, S, implicit, before, C.candidates(), M, cur, have_hist));
+    if (!implicit) cur ^= 1;
+    implicit = false;
+    if (have_hist) QE_TRY(sort_read_back(ctx, M, SORT_HEAD + SORT_HIST_B));
+  }
+
+  const int64_t cand = stats[2] = C.candidates();
+  if (cand <= SORT_SMALL_MAX) {
+    if (implicit)
+      hipLaunchKernelGGL(k_sort_small, dim3(1), dim3(SORT_SMALL_THREADS), 0, ctx->stream, D, (int32_t)n, (int32_t)m, out,
+                         M.err);
+    else
+      hipLaunchKernelGGL(k_sort_small_rows, dim3(1), dim3(SORT_SMALL_THREADS), 0, ctx->stream, D, (int32_t)cand, (int32_t)n,
+                         (const int32_t*)M.idx[cur], (int32_t)m, out, M.err);
+    QE_TRY(launch_check("k_sort_small"));
+    if (promised) QE_TRY(sort_read_back(ctx, M, 4));
+    return QE_OK;
+  }
+  if (implicit) QE_TRY(topk_mem_pairs(ctx, pairs, n, &M));  // no step ran: the candidates are all n rows
+  QE_TRY(sort_multi(ctx, D, n, cand, !implicit, M, cur, &cur));
+  QE_HIP(hipMemcpyAsync(out, M.idx[cur], (size_t)m * 4, hipMemcpyDeviceToDevice, ctx->stream));
+  return QE_OK;
+}
+
+}  // namespace qe
+
+using namespace qe;
+
+extern "C" {
+
+int qe_sort_layout(int32_t* tile_rows, int32_t* small_max) {
+  if (tile_rows) *tile_rows = SORT_TILE;
+  if (small_max) *small_max = SORT_SMALL_MAX;
+  return QE_OK;
+}
+
+int qe_sort_indices(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, int32_t nkeys, int64_t limit,
+                    qe_column* out_indices) {
+  QE_TRY(ctx_enter(ctx));
+  return sort_impl(ctx, "sort", keys, flags, nkeys, limit, out_indices, nullptr);
+}
+
+int qe_topk_indices(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, int32_t nkeys, int64_t k, int32_t mode,
+                    qe_column* out_indices) {
+  QE_TRY(ctx_enter(ctx));
+  QE_CHECK(k >= 0, QE_ERR_INVALID_ARG, "topk: k = %lld is negative", (long long)k);
+  QE_CHECK(mode == QE_TOPK_AUTO || mode == QE_TOPK_SELECT || mode == QE_TOPK_SORT, QE_ERR_INVALID_ARG,
+           "topk: unknown mode %d", mode);
+  int64_t n;
+  QE_TRY(sort_check_args("topk", keys, flags, nkeys, out_indices, &n));
+  const int64_t m = std::min(k, n);  // from here on only m is used: k may be INT64_MAX
+  const bool select = mode == QE_TOPK_SELECT ? n > 0 : mode == QE_TOPK_AUTO && topk_use_select(n, m, SORT_SMALL_MAX);
+  int64_t* stats = ctx->topk_stats;
+  stats[0] = select ? 1 : 0;
+  stats[1] = stats[3] = 0;
+  stats[2] = select ? 0 : n;
+  if (!select) return sort_impl(ctx, "topk", keys, flags, nkeys, m, out_indices, &stats[3]);
+  QE_TRY(sort_check_out("topk", out_indices, m));
+  if (m == 0) return QE_OK;
+  SortMem M;
+  M.who = "topk";
+  const int st = topk_select(ctx, keys, flags, nkeys, n, m, (int32_t*)out_indices->values, M, stats);
+  stats[3] = M.readbacks;
+  return st;
+}
+
+int qe_topk_last_stats(qe_ctx* ctx, int64_t stats[4]) {
+  QE_TRY(ctx_enter(ctx));
+  QE_CHECK(stats != nullptr, QE_ERR_INVALID_ARG, "topk: null stats");
+  for (int i = 0; i < 4; ++i) stats[i] = ctx->topk_stats[i];
   return QE_OK;
 }
 

@@ -47,6 +47,7 @@ OP_AND, OP_OR, OP_NOT, OP_IS_NULL, OP_IS_NOT_NULL = 20, 21, 22, 23, 24
 AGG_SUM, AGG_MIN, AGG_MAX, AGG_COUNT, AGG_COUNT_STAR, AGG_AVG = 1, 2, 3, 4, 5, 6
 
 SORT_DESC, SORT_NULLS_FIRST = 1, 2  # qe_sort_indices flag bits (0: ascending, nulls last)
+TOPK_AUTO, TOPK_SELECT, TOPK_SORT = 0, 1, 2  # qe_topk_indices modes
 JOIN_INNER, JOIN_LEFT = 0, 1  # qe_join_probe kinds
 
 MAX_KEYS, MAX_AGGS, MAX_COLS, MAX_TERMS, MAX_TOKENS = 4, 8, 8, 8, 16
@@ -242,6 +243,8 @@ SIGNATURES = [
     ("qe_sort_indices", C.c_int, [_P, _COLP, C.POINTER(C.c_int32), C.c_int32, C.c_int64, _COLP]),
     ("qe_take", C.c_int, [_P, _COLP, _COLP, C.c_int32, _COLP, _I64P]),
     ("qe_sort_layout", C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
+    ("qe_topk_indices", C.c_int, [_P, _COLP, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int32, _COLP]),
+    ("qe_topk_last_stats", C.c_int, [_P, _I64P]),
     ("qe_join_build", C.c_int, [_P, _COLP, _PP]),
     ("qe_join_destroy", C.c_int, [_P]),
     ("qe_join_probe", C.c_int, [_P, _COLP, C.c_int32, _COLP, _COLP, _I64P]),

@@ -232,6 +232,28 @@ def sort_indices(keys: Sequence[DeviceColumn], flags: Sequence[int], limit: Opti
     return out
 
 
+def topk_indices(keys: Sequence[DeviceColumn], flags: Sequence[int], k: int, mode: int = N.TOPK_AUTO) -> DeviceColumn:
+    """qe_topk_indices: the first min(k, n) row indices of the stable order of `keys` (sort_indices
+    with limit=k, entry for entry). mode: N.TOPK_AUTO picks radix selection for a small k and the
+    full sort otherwise; N.TOPK_SELECT / N.TOPK_SORT force one."""
+    ctx = keys[0].ctx
+    out = DeviceColumn.empty(N.TYPE_INT32, max(0, min(int(k), keys[0].length)), False, ctx=ctx)
+    kc = (N.QeColumn * len(keys))(*[c.as_c() for c in keys])
+    fl = (N.C.c_int32 * len(keys))(*[int(f) for f in flags])
+    oc = out.as_c()
+    N.check(N.lib().qe_topk_indices(ctx.handle, kc, fl, len(keys), int(k), int(mode), N.C.byref(oc)))
+    out.length = oc.length
+    return out
+
+
+def topk_last_stats(ctx):
+    """qe_topk_last_stats: (path taken: 0 sort / 1 selection, digit steps, candidates handed to the
+    final sort, host read-backs) of the context's last topk_indices call."""
+    st = (N.C.c_int64 * 4)()
+    N.check(N.lib().qe_topk_last_stats(ctx.handle, st))
+    return tuple(st)
+
+
 def take(indices: DeviceColumn, cols: Sequence[DeviceColumn],
          utf8_bytes: Optional[Sequence[Optional[int]]] = None) -> List[DeviceColumn]:
     """qe_take: row indices[i] of every column, validity included. utf8_bytes[c]: the value bytes
@@ -553,7 +575,7 @@ class SortExec(PhysicalPlan):
             if not isinstance(k, DeviceColumn):
                 raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "a sort expression must evaluate to a column")
         flags = [(0 if asc else N.SORT_DESC) | (N.SORT_NULLS_FIRST if nf else 0) for _, asc, nf in self.sort_exprs]
-        idx = sort_indices(keys, flags, self.limit)
+        idx = sort_indices(keys, flags) if self.limit is None else topk_indices(keys, flags, self.limit)
         yield RecordBatch(schema, take(idx, batch.fields))
 
     def __repr__(self) -> str:
