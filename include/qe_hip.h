@@ -310,6 +310,69 @@ int qe_topk_indices(qe_ctx* ctx, const qe_column* keys, const int32_t* flags, in
  * [3] = host read-backs. */
 int qe_topk_last_stats(qe_ctx* ctx, int64_t stats[4]);
 
+/* ---- window functions: fn(...) OVER (PARTITION BY ... ORDER BY ...) (build-defined) ----------
+ * One window per evaluation: the rows in the stable order of qe_sort_indices over (partition keys
+ * ascending, then order keys), which the caller passes as the INT32 permutation `order`. A partition
+ * is a maximal run of rows equal on every partition key, a peer group a maximal run within it equal
+ * on every order key, both by the sort's equality (a null equals a null, every NaN is one value,
+ * -0.0 != +0.0, UTF8 by bytes). Results are written at the INPUT's row positions. */
+#define QE_WIN_ROW_NUMBER 1  /* INT64, never null; the frame is ignored */
+#define QE_WIN_RANK 2        /* the row number of the peer group's first row */
+#define QE_WIN_DENSE_RANK 3  /* the peer group's ordinal in its partition */
+#define QE_WIN_COUNT_STAR 4  /* rows of the frame; INT64, never null */
+#define QE_WIN_COUNT 5       /* non-null rows of the frame (any input type); INT64, never null */
+#define QE_WIN_SUM 6         /* INT64 / INT32 -> INT64, wraps, nulls skipped; null while the frame has no value */
+#define QE_WIN_MIN 7         /* INT64 / INT32 / DATE32 / UINT8 / FLOAT64 -> the input's type */
+#define QE_WIN_MAX 8         /* (MaxAccumulator's fold over the frame in window order, below) */
+#define QE_WIN_LAG 9         /* x of the row `offset` positions earlier in the partition, nulls included */
+#define QE_WIN_LEAD 10       /* ... later; null where that position lies outside the partition */
+/* Every frame starts at the partition's first row and ends at: */
+#define QE_FRAME_ROWS 0      /* the current row */
+#define QE_FRAME_RANGE 1     /* the last row of the current row's peer group */
+#define QE_FRAME_PARTITION 2 /* the partition's last row */
+typedef struct qe_window_fn {
+  int32_t fn;     /* QE_WIN_* */
+  int32_t frame;  /* QE_FRAME_*; must be one of them for every function, read by COUNT* / SUM / MIN / MAX */
+  int32_t input;  /* index into `inputs` (COUNT, SUM, MIN, MAX, LAG, LEAD); ignored otherwise */
+  int32_t reserved;
+  int64_t offset; /* LAG / LEAD: any int64 >= 0 (0 gives x itself); ignored otherwise */
+} qe_window_fn;
+
+/* Run boundaries along a permutation. `order`: INT32 without validity, n rows; keys: 0..QE_MAX_KEYS
+ * columns of n rows, any type a sort key may have (UTF8 compared by bytes at any length). `starts`:
+ * BOOL without validity, capacity >= n rows, whole 32-bit words written: bit i is set iff i = 0 or
+ * rows order[i-1] and order[i] differ on some key (nkeys = 0 sets only bit 0); the bits at and past n
+ * of the last word are 0. An entry of `order` outside [0, n) reads nothing and starts a run (and ends
+ * the one before it); qe_window_eval is the call that reports it. n = 0 writes nothing.
+ * Stream-ordered: queued on the ctx stream, no working memory, no host wait. */
+int qe_window_boundaries(qe_ctx* ctx, const qe_column* keys, int32_t nkeys, const qe_column* order,
+                         qe_column* starts);
+/* Evaluates nfns <= QE_MAX_AGGS functions over ninputs <= QE_MAX_COLS input columns of n rows
+ * (n = part_starts->length <= 2^31-1). part_starts / peer_starts: the boundaries of the partition
+ * keys and of partition + order keys (BOOL without validity, n rows; every partition start must be a
+ * peer start). outs[k]: the result of fns[k] at the input's row positions, capacity >= n rows
+ * (QE_ERR_CAPACITY), type INT64 for the ranks, the counts and SUM, the input's type for MIN / MAX /
+ * LAG / LEAD; a validity buffer (whole 32-bit words) is required for SUM / MIN / MAX / LAG / LEAD and
+ * written for the others when present. A null result's value is 0.
+ * MIN / MAX of FLOAT64: NaN (the quiet NaN 0x7FF8000000000000) if the frame's first non-null value
+ * is NaN, otherwise the extreme of the non-NaN values; of values that compare equal (-0.0, +0.0) the
+ * earliest in window order.
+ * QE_ERR_UNSUPPORTED: SUM of FLOAT64 / DATE32 / UINT8 / BOOL / UTF8, MIN / MAX / LAG / LEAD of BOOL /
+ * UTF8. QE_ERR_INVALID_ARG: an unknown function or frame, an offset < 0, an input index outside
+ * [0, ninputs), `order` not INT32 or not of n rows, an input or boundary column of another length, an
+ * output of the wrong type or without the validity buffer it needs. A refused call writes nothing.
+ * An entry of `order` outside [0, n) reads and writes nothing out of range and fails the call with
+ * QE_ERR_INVALID_ARG (the outputs are then unspecified, the inputs untouched).
+ * Queued on the ctx stream with working memory from the library's allocator, released
+ * stream-ordered; n <= small_max (qe_window_layout) is one launch of one workgroup. The one host
+ * wait is the read of the out-of-range flag at the end of the call. */
+int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_starts,
+                   const qe_column* peer_starts, const qe_column* inputs, int32_t ninputs,
+                   const qe_window_fn* fns, int32_t nfns, qe_column* outs);
+/* Measurement hook: positions per tile of the multi-workgroup scans (a tile of the scans over the
+ * boundary bitmaps' words covers 32 x tile_rows rows), and the largest n the one-workgroup path takes. */
+int qe_window_layout(int32_t* tile_rows, int32_t* small_max);
+
 /* ---- equi-JOIN (build-defined; the reference's SQL has no JOIN) ------------------------------
  * A hash table is built once from the key column of one side (the build side) and probed by
  * batches of the other. The result is (probe row, build row) index pairs that qe_take /

@@ -371,4 +371,80 @@ class AvgExpression(AggregateExpression):
     fn, name = N.AGG_AVG, "AVG"
 
 
+# ---- window expressions: fn(...) OVER (PARTITION BY ... ORDER BY ...) (build-defined) ----
+class WindowExpression:
+    """One function of a WindowExec. expr: the input expression (None for the functions without
+    one); frame: N.FRAME_ROWS / FRAME_RANGE / FRAME_PARTITION (read by the aggregates only; every
+    frame starts at the partition's first row); offset: LAG / LEAD."""
+
+    fn: int = 0
+    name: str = "?"
+
+    def __init__(self, expr: Optional[Expression] = None, frame: int = N.FRAME_RANGE, offset: int = 0):
+        self.expr = expr
+        self.frame = int(frame)
+        self.offset = int(offset)
+
+    def inputExpression(self) -> Optional[Expression]:  # noqa: N802
+        return self.expr
+
+    def output_type(self, input_type: Optional[int]) -> int:
+        """INT64 for the ranks, the counts and SUM; the input's type for MIN / MAX / LAG / LEAD."""
+        return input_type if self.fn in (N.WIN_MIN, N.WIN_MAX, N.WIN_LAG, N.WIN_LEAD) else N.TYPE_INT64
+
+    def __repr__(self) -> str:
+        return f"{self.name}({self.expr if self.expr is not None else ''})"
+
+
+class RowNumber(WindowExpression):
+    fn, name = N.WIN_ROW_NUMBER, "ROW_NUMBER"
+
+    def __init__(self):
+        super().__init__(None)
+
+
+class Rank(RowNumber):
+    fn, name = N.WIN_RANK, "RANK"
+
+
+class DenseRank(RowNumber):
+    fn, name = N.WIN_DENSE_RANK, "DENSE_RANK"
+
+
+class WindowCount(WindowExpression):
+    """COUNT(x) over the frame, or COUNT(*) when expr is None."""
+
+    name = "COUNT"
+
+    def __init__(self, expr: Optional[Expression] = None, frame: int = N.FRAME_RANGE):
+        super().__init__(expr, frame)
+        self.fn = N.WIN_COUNT_STAR if expr is None else N.WIN_COUNT
+
+
+class WindowSum(WindowExpression):
+    fn, name = N.WIN_SUM, "SUM"
+
+    def __init__(self, expr: Expression, frame: int = N.FRAME_RANGE):
+        super().__init__(expr, frame)
+
+
+class WindowMin(WindowSum):
+    fn, name = N.WIN_MIN, "MIN"
+
+
+class WindowMax(WindowSum):
+    fn, name = N.WIN_MAX, "MAX"
+
+
+class Lag(WindowExpression):
+    fn, name = N.WIN_LAG, "LAG"
+
+    def __init__(self, expr: Expression, offset: int = 1):
+        super().__init__(expr, N.FRAME_ROWS, offset)
+
+
+class Lead(Lag):
+    fn, name = N.WIN_LEAD, "LEAD"
+
+
 Operand = Union[DeviceColumn, ScalarColumn]

@@ -49,6 +49,10 @@ AGG_SUM, AGG_MIN, AGG_MAX, AGG_COUNT, AGG_COUNT_STAR, AGG_AVG = 1, 2, 3, 4, 5, 6
 SORT_DESC, SORT_NULLS_FIRST = 1, 2  # qe_sort_indices flag bits (0: ascending, nulls last)
 TOPK_AUTO, TOPK_SELECT, TOPK_SORT = 0, 1, 2  # qe_topk_indices modes
 JOIN_INNER, JOIN_LEFT = 0, 1  # qe_join_probe kinds
+# qe_window_eval functions and frames (every frame starts at the partition's first row)
+(WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT_STAR, WIN_COUNT, WIN_SUM, WIN_MIN, WIN_MAX, WIN_LAG,
+ WIN_LEAD) = range(1, 11)
+FRAME_ROWS, FRAME_RANGE, FRAME_PARTITION = 0, 1, 2
 
 MAX_KEYS, MAX_AGGS, MAX_COLS, MAX_TERMS, MAX_TOKENS = 4, 8, 8, 8, 16
 TOK_COL, TOK_LIT, TOK_ADD, TOK_SUB, TOK_MUL, TOK_DIV = 1, 2, 3, 4, 5, 6
@@ -132,6 +136,11 @@ class QeGlobalAgg(C.Structure):
 
 class QeAggDesc(C.Structure):
     _fields_ = [("fn", C.c_int32), ("input_type", C.c_int32)]
+
+
+class QeWindowFn(C.Structure):
+    _fields_ = [("fn", C.c_int32), ("frame", C.c_int32), ("input", C.c_int32), ("reserved", C.c_int32),
+                ("offset", C.c_int64)]
 
 
 class QePredTerm(C.Structure):
@@ -245,6 +254,9 @@ SIGNATURES = [
     ("qe_sort_layout", C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("qe_topk_indices", C.c_int, [_P, _COLP, C.POINTER(C.c_int32), C.c_int32, C.c_int64, C.c_int32, _COLP]),
     ("qe_topk_last_stats", C.c_int, [_P, _I64P]),
+    ("qe_window_boundaries", C.c_int, [_P, _COLP, C.c_int32, _COLP, _COLP]),
+    ("qe_window_eval", C.c_int, [_P, _COLP, _COLP, _COLP, _COLP, C.c_int32, C.POINTER(QeWindowFn), C.c_int32, _COLP]),
+    ("qe_window_layout", C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("qe_join_build", C.c_int, [_P, _COLP, _PP]),
     ("qe_join_destroy", C.c_int, [_P]),
     ("qe_join_probe", C.c_int, [_P, _COLP, C.c_int32, _COLP, _COLP, _I64P]),

@@ -304,6 +304,131 @@ def _take(indices: DeviceColumn, cols: Sequence[DeviceColumn], utf8_bytes, or_nu
 
 
 # ---------------------------------------------------------------------------------------------------
+# Window functions (build-defined): run boundaries along a sort, scans, per-row evaluation
+# ---------------------------------------------------------------------------------------------------
+_WIN_NULLABLE = (N.WIN_SUM, N.WIN_MIN, N.WIN_MAX, N.WIN_LAG, N.WIN_LEAD)
+_WIN_INPUT_TYPE = (N.WIN_MIN, N.WIN_MAX, N.WIN_LAG, N.WIN_LEAD)
+
+
+def window_layout():
+    """(positions per tile of the multi-workgroup scans, largest single-workgroup n)."""
+    t, s = N.C.c_int32(), N.C.c_int32()
+    N.check(N.lib().qe_window_layout(N.C.byref(t), N.C.byref(s)))
+    return t.value, s.value
+
+
+def window_boundaries(keys: Sequence[DeviceColumn], order: DeviceColumn) -> DeviceColumn:
+    """qe_window_boundaries: the BOOL column whose bit i says that position i of the permutation
+    `order` starts a run of rows equal on every key (no keys: only bit 0). Stream-ordered."""
+    ctx = order.ctx
+    out = DeviceColumn.empty(N.TYPE_BOOL, order.length, False, ctx=ctx)
+    kc = (N.QeColumn * max(len(keys), 1))(*[k.as_c() for k in keys])
+    oc, sc = order.as_c(), out.as_c()
+    N.check(N.lib().qe_window_boundaries(ctx.handle, kc, len(keys), N.C.byref(oc), N.C.byref(sc)))
+    return out
+
+
+def window_eval(order: DeviceColumn, part_starts: DeviceColumn, peer_starts: DeviceColumn,
+                inputs: Sequence[DeviceColumn], fns, outs: Optional[Sequence[DeviceColumn]] = None) -> List[DeviceColumn]:
+    """qe_window_eval: fns is a sequence of (fn, frame, input index, offset); one output column per
+    function at the input's row positions (`outs`: caller-provided outputs instead of fresh ones)."""
+    ctx = order.ctx
+    n = part_starts.length
+    if outs is None:
+        outs = []
+        for fn, _, inp, _ in fns:
+            t = inputs[inp].type if fn in _WIN_INPUT_TYPE and 0 <= inp < len(inputs) else N.TYPE_INT64
+            outs.append(DeviceColumn.empty(t if t in N.FIXED_WIDTH else N.TYPE_INT64, n, fn in _WIN_NULLABLE, ctx=ctx))
+    fc = (N.QeWindowFn * max(len(fns), 1))(*[N.QeWindowFn(int(fn), int(fr), int(inp), 0, int(off)) for fn, fr, inp, off in fns])
+    ic = (N.QeColumn * max(len(inputs), 1))(*[c.as_c() for c in inputs])
+    oc = (N.QeColumn * max(len(outs), 1))(*[o.as_c() for o in outs])
+    rc, pc, gc = order.as_c(), part_starts.as_c(), peer_starts.as_c()
+    N.check(N.lib().qe_window_eval(ctx.handle, N.C.byref(rc), N.C.byref(pc), N.C.byref(gc), ic, len(inputs), fc, len(fns), oc))
+    return list(outs)
+
+
+class WindowExec(PhysicalPlan):
+    """fn(...) OVER (PARTITION BY ... ORDER BY ...) (build-defined). A pipeline breaker like
+    SortExec: drains its input into one batch (concat_batches), evaluates the key and input
+    expressions, sorts by (partition keys ascending, then order keys) to row indices
+    (qe_sort_indices), finds the partition and peer boundaries along them (qe_window_boundaries,
+    twice) and evaluates every function in one qe_window_eval. partition_by: expressions; order_by:
+    (Expression, ascending, nulls_first) triples; functions: WindowExpressions. Yields ONE batch in the
+    INPUT's row order: the input's columns, then one column per function (`schema` names them). An
+    empty input gives a 0-row batch; without keys the whole input is one partition of peers and no
+    sort runs."""
+
+    def __init__(self, input: PhysicalPlan, partition_by, order_by, functions, schema: Schema):  # noqa: A002
+        if len(partition_by) + len(order_by) > N.MAX_KEYS:
+            raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG,
+                                             f"a window takes at most {N.MAX_KEYS} partition and order keys together")
+        if len(functions) > N.MAX_AGGS:
+            raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG, f"a window takes at most {N.MAX_AGGS} functions")
+        self.input = input
+        self.partition_by = list(partition_by)
+        self.order_by = [(e, bool(asc), bool(nf)) for e, asc, nf in order_by]
+        self.functions = list(functions)
+        self._schema = schema
+
+    def schema(self) -> Schema:
+        return self._schema
+
+    def children(self) -> List[PhysicalPlan]:
+        return [self.input]
+
+    def execute(self) -> Iterator[RecordBatch]:
+        import torch
+
+        from .columnar import Context, concat_batches
+
+        schema = self._schema
+        batches = [b for b in self.input.execute() if b.fields]
+        for b in batches:
+            for c in b.fields:
+                if not isinstance(c, DeviceColumn):
+                    raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "window input must be device columns")
+        if not batches:
+            ctx = Context.get(0)
+            yield RecordBatch(schema, [
+                DeviceColumn.from_strings([], ctx=ctx) if f.dataType == N.TYPE_UTF8
+                else DeviceColumn.empty(f.dataType, 0, True, ctx=ctx) for f in schema.fields])
+            return
+        batch = concat_batches(batches)
+        part = [e.evaluate(batch) for e in self.partition_by]
+        okeys = [e.evaluate(batch) for e, _, _ in self.order_by]
+        inputs: List[DeviceColumn] = []
+        fns = []
+        for f in self.functions:
+            slot = 0
+            if f.expr is not None:
+                cv = f.expr.evaluate(batch)
+                slot = next((i for i, c in enumerate(inputs) if c is cv), len(inputs))
+                if slot == len(inputs):
+                    inputs.append(cv)
+            fns.append((f.fn, f.frame, slot, f.offset))
+        for c in part + okeys + inputs:
+            if not isinstance(c, DeviceColumn):
+                raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "a window key or input must evaluate to a column")
+        if len(inputs) > N.MAX_COLS:
+            raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG, f"a window takes at most {N.MAX_COLS} distinct inputs")
+        ctx = batch.fields[0].ctx
+        n = batch.fields[0].length
+        keys = part + okeys
+        if keys:
+            flags = [0] * len(part) + [(0 if asc else N.SORT_DESC) | (N.SORT_NULLS_FIRST if nf else 0)
+                                       for _, asc, nf in self.order_by]
+            order = sort_indices(keys, flags)
+        else:
+            order = DeviceColumn(N.TYPE_INT32, n, torch.arange(max(n, 1), dtype=torch.int32, device=ctx.torch_device), ctx=ctx)
+        part_starts = window_boundaries(part, order)
+        peer_starts = window_boundaries(keys, order) if okeys else part_starts
+        yield RecordBatch(schema, list(batch.fields) + window_eval(order, part_starts, peer_starts, inputs, fns))
+
+    def __repr__(self) -> str:
+        return f"WindowExec: partition_by={self.partition_by}, order_by={self.order_by}, functions={self.functions}"
+
+
+# ---------------------------------------------------------------------------------------------------
 # Equi-join (build-defined, DESIGN §4): device hash build / probe -> row-index pairs
 # ---------------------------------------------------------------------------------------------------
 class JoinTable:
