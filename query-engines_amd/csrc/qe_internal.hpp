@@ -202,7 +202,7 @@ inline int selproj_resident_group(int R) { return R < 8 ? R : 8; }
 // Exclusive scan of n int64 on the ctx stream (one block); out[n] = total. (qe_filter.hip)
 int exclusive_scan_i64(qe_ctx* ctx, const int64_t* in, int64_t* out, int64_t n);
 // UTF-8 gather from (source byte offset, length) pairs: length scan, output offsets, byte copy
-// (qe_filter.hip; shared by qe_filter_apply and qe_take).
+// (qe_filter.hip; shared by qe_filter_apply and qe_take.hip's qe_take).
 int64_t utf8_gather_tiles(int64_t rows);
 int utf8_gather_lengths(qe_ctx* ctx, const int2* sl, int64_t rows, int64_t* tsum);
 int utf8_gather_copy(qe_ctx* ctx, const int2* sl, int64_t rows, const int64_t* tsum, const uint8_t* src,

@@ -22,11 +22,10 @@
 //                   every lane writes its rows' runs
 // qe_join_probe_mask
 //   k_join_mask   : one row per lane, the BOOL words built per wave with __ballot; no host wait
-#include "qe_internal.hpp"
+#include "qe_rows.hpp"
 #include "qe_join_plan.hpp"
 
 #include <new>
-#include <vector>
 
 struct qe_join {
   qe_ctx* ctx = nullptr;
@@ -60,17 +59,8 @@ constexpr int64_t JOIN_COOP_MIN = QE_JOIN_COOP_MIN;
 
 // The key word of row i; false for a null row.
 __device__ __forceinline__ bool join_row_word(const JKey& K, int64_t i, uint64_t* w) {
-  if (K.validity && !((K.validity[i >> 3] >> (i & 7)) & 1)) return false;
-  uint64_t raw;
-  switch (K.type) {
-    case QE_TYPE_INT64:
-    case QE_TYPE_FLOAT64: raw = ((const uint64_t*)K.values)[i]; break;
-    case QE_TYPE_INT32:
-    case QE_TYPE_DATE32: raw = ((const uint32_t*)K.values)[i]; break;
-    case QE_TYPE_UINT8: raw = ((const uint8_t*)K.values)[i]; break;
-    default: raw = (((const uint8_t*)K.values)[i >> 3] >> (i & 7)) & 1; break;  // BOOL
-  }
-  *w = join_key_word(K.type, raw);
+  if (!row_valid(K.validity, i)) return false;
+  *w = join_key_word(K.type, load_fixed_raw(K.type, K.values, i));
   return true;
 }
 
@@ -96,7 +86,7 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_valid(const uint8_t* __re
                                                              unsigned long long* __restrict__ out) {
   uint64_t c = 0;
   for (int64_t i = blockIdx.x * (int64_t)JOIN_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * JOIN_THREADS)
-    c += (validity[i >> 3] >> (i & 7)) & 1;
+    c += row_valid(validity, i);
   c = wave_sum(c);
   if ((threadIdx.x & 63) == 0 && c) atomicAdd(out, (unsigned long long)c);
 }
@@ -260,32 +250,11 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_mask(JKey K, int64_t n, c
       int64_t pairs;
       b = ((probe_row(K, i, tab, S, false, &pairs) >> 32) != 0) != (anti != 0);
     }
-    const uint64_t bits = __ballot(b);
-    if (lane == 0 && 2 * c < nwords) mask[2 * c] = (uint32_t)bits;
-    if (lane == 1 && 2 * c + 1 < nwords) mask[2 * c + 1] = (uint32_t)(bits >> 32);
+    store_bits64(mask, c, nwords, __ballot(b), lane);
   }
 }
 
 namespace {
-
-struct Blocks {  // working memory of one call: freed stream-ordered when the call returns
-  qe_ctx* ctx;
-  std::vector<void*> ps;
-  explicit Blocks(qe_ctx* c) : ctx(c) {}
-  ~Blocks() {
-    for (void* p : ps) dev_free(ctx, p);
-  }
-  int alloc(size_t bytes, void** out) {
-    QE_TRY(dev_alloc(ctx, bytes ? bytes : 8, out));
-    ps.push_back(*out);
-    return QE_OK;
-  }
-  void keep(void* p) { ps.erase(std::find(ps.begin(), ps.end(), p)); }  // the caller owns it from here
-};
-
-int stride_grid(const qe_ctx* ctx, int64_t n) {
-  return (int)std::max<int64_t>(1, std::min<int64_t>((int64_t)div_up((uint64_t)n, JOIN_THREADS), (int64_t)ctx->num_cus * 8));
-}
 
 int check_key(const char* what, const qe_column* key) {
   QE_CHECK(key != nullptr, QE_ERR_INVALID_ARG, "%s: null key column", what);

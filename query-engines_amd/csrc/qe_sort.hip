@@ -1,5 +1,5 @@
 // ORDER BY (build-defined operator): stable multi-key sort to row indices, and
-// the gather by row index that applies them.
+// the first k rows of that order (qe_take.hip gathers by the indices).
 //
 // qe_sort_indices
 //   Every key becomes bits of one long unsigned key (qe_sort_key.hpp), most significant key first;
@@ -20,14 +20,11 @@
 //   down (host rules: qe_topk_plan.hpp): k_topk_words (digit histograms; the first pass writes
 //   nothing else), per digit step k_topk_count / exclusive scan / k_topk_compact over a candidate
 //   list kept in row order, then k_sort_small_rows or the passes above over the candidates.
-// qe_take
-//   k_take: one row per lane, validity / BOOL words built per wave with __ballot; UTF8 through the
-//   (start, length) pairs, length scan and byte copy of qe_filter.hip.
-// qe_take_or_null
-//   k_take<true>: index -1 is "no row" and gives a null row (the build side of a LEFT join).
 // sort_pairs
 //   the count / scan / scatter passes over a caller's (word, index) buffers (qe_join.hip).
-#include "qe_internal.hpp"
+// One body each serves the two encoders (encode_words), the two small sorts (sort_small) and every
+// digit pass (sort_digit_pass).
+#include "qe_rows.hpp"
 #include "qe_sort_key.hpp"
 #include "qe_topk_plan.hpp"
 
@@ -93,19 +90,11 @@ __device__ __forceinline__ uint64_t sort_word(const SortDesc& D, int64_t r, int6
     const bool in_n = K.lo_n >= b0 && K.lo_n < b1;
     const bool in_c = K.mode == SK_UTF8 && k >= K.cw0 && k < K.cw0 + K.nchunks;
     if (!(in_v || in_n || in_c)) continue;
-    const bool valid = !K.validity || ((K.validity[r >> 3] >> (r & 7)) & 1);
+    const bool valid = row_valid(K.validity, r);
     if (in_n) w |= sort_null_bit(valid, K.flags) << (K.lo_n - b0);
     if (!valid) continue;
     if (K.mode == SK_FIXED) {
-      uint64_t raw;
-      switch (K.type) {
-        case QE_TYPE_INT64:
-        case QE_TYPE_FLOAT64: raw = ((const uint64_t*)K.values)[r]; break;
-        case QE_TYPE_INT32:
-        case QE_TYPE_DATE32: raw = ((const uint32_t*)K.values)[r]; break;
-        case QE_TYPE_UINT8: raw = ((const uint8_t*)K.values)[r]; break;
-        default: raw = (((const uint8_t*)K.values)[r >> 3] >> (r & 7)) & 1; break;  // BOOL
-      }
+      const uint64_t raw = load_fixed_raw(K.type, K.values, r);
       w |= sort_place(sort_field(sort_enc_fixed(K.type, raw), K.vbits, true, K.flags), K.lo_v, k);
     } else {
       const int32_t s = K.offsets[r];
@@ -149,28 +138,71 @@ __global__ void __launch_bounds__(256) k_utf8_max_len(const int32_t* __restrict_
   if ((threadIdx.x & 63) == 0 && mx > 0) atomicMax(out, mx);
 }
 
-// words[i] = word k of row perm[i] (perm NULL: row i, and idx_out[i] = i); hist[256 g + v] += rows
-// whose digit g of that word is v.
+// A workgroup's 8 digit histograms of a word in LDS: cleared, filled by hist_add, then added to the
+// global ones (the caller puts a barrier between the steps).
+template <int THREADS>
+__device__ __forceinline__ void hist_clear(uint32_t* h) {
+  for (int j = threadIdx.x; j < 8 * 256; j += THREADS) h[j] = 0;
+}
+template <int THREADS>
+__device__ __forceinline__ void hist_flush(const uint32_t* h, uint32_t* __restrict__ hist) {
+  for (int j = threadIdx.x; j < 8 * 256; j += THREADS)
+    if (h[j]) atomicAdd(&hist[j], h[j]);
+}
+
+// Word k of the rows that m list entries name, and hist[256 g + v] += encoded rows whose digit g of
+// that word is v. The list:
+//   TW_PERM : the sort's permutation `list` of rows 0 .. m - 1 -> words[i]; list NULL: row i, and
+//             iota[i] = i
+//   TW_ALL  : the top-k's implicit list, rows 0 .. m - 1; nothing but the histograms is written
+//   TW_TIED : the tied entries of the candidate list (top-k section below) -> words[i]
+//   TW_SORT : every entry of the candidate list -> words[i]; `strip`: the flag bits leave `list` (the
+//             final sort's first word: from here on the list is the sort's permutation)
+constexpr uint32_t TOPK_SURE = 0x80000000u;
 constexpr int ENC_THREADS = 256;
-__global__ void __launch_bounds__(ENC_THREADS) k_sort_encode(SortDesc D, int64_t k, int64_t n,
-                                                              const int32_t* __restrict__ perm,
-                                                              uint64_t* __restrict__ words, int32_t* __restrict__ idx_out,
-                                                              uint32_t* __restrict__ hist, unsigned* __restrict__ err) {
+enum { TW_ALL = 0, TW_TIED = 1, TW_SORT = 2, TW_PERM = 3 };
+template <int MODE>
+__device__ __forceinline__ void encode_words(const SortDesc& D, int64_t k, int64_t nrows, int64_t m,
+                                             int32_t* __restrict__ list, uint64_t* __restrict__ words,
+                                             int32_t* __restrict__ iota, int strip, uint32_t* __restrict__ hist,
+                                             unsigned* __restrict__ err) {
   __shared__ uint32_t h[8 * 256];
-  for (int j = threadIdx.x; j < 8 * 256; j += ENC_THREADS) h[j] = 0;
+  hist_clear<ENC_THREADS>(h);
   __syncthreads();
-  for (int64_t i = blockIdx.x * (int64_t)ENC_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * ENC_THREADS) {
-    int64_t r = perm ? (int64_t)perm[i] : i;
-    if ((uint64_t)r >= (uint64_t)n) r = 0;  // (a permutation never is)
+  for (int64_t i = blockIdx.x * (int64_t)ENC_THREADS + threadIdx.x; i < m; i += (int64_t)gridDim.x * ENC_THREADS) {
+    int64_t r = i;
+    if (MODE == TW_PERM) {
+      if (list) r = (int64_t)list[i];
+    } else if (MODE != TW_ALL) {
+      const uint32_t c = (uint32_t)list[i];
+      if (MODE == TW_TIED && (c & TOPK_SURE)) continue;
+      r = (int64_t)(c & ~TOPK_SURE);
+      if (MODE == TW_SORT && strip) list[i] = (int32_t)r;
+    }
+    if ((uint64_t)r >= (uint64_t)nrows) r = 0;  // (a permutation or a candidate never is)
     const uint64_t w = sort_word(D, r, k, err);
-    words[i] = w;
-    if (idx_out) idx_out[i] = (int32_t)i;
+    if (MODE != TW_ALL) words[i] = w;
+    if (MODE == TW_PERM && iota) iota[i] = (int32_t)i;
 #pragma unroll
     for (int g = 0; g < 8; ++g) hist_add(h + 256 * g, (uint32_t)(w >> (8 * g)) & 255u);
   }
   __syncthreads();
-  for (int j = threadIdx.x; j < 8 * 256; j += ENC_THREADS)
-    if (h[j]) atomicAdd(&hist[j], h[j]);
+  hist_flush<ENC_THREADS>(h, hist);
+}
+
+__global__ void __launch_bounds__(ENC_THREADS) k_sort_encode(SortDesc D, int64_t k, int64_t n,
+                                                              const int32_t* __restrict__ perm,
+                                                              uint64_t* __restrict__ words, int32_t* __restrict__ idx_out,
+                                                              uint32_t* __restrict__ hist, unsigned* __restrict__ err) {
+  encode_words<TW_PERM>(D, k, n, n, const_cast<int32_t*>(perm), words, idx_out, 0, hist, err);  // (TW_PERM only reads it)
+}
+
+template <int MODE>
+__global__ void __launch_bounds__(ENC_THREADS) k_topk_words(SortDesc D, int64_t k, int64_t nrows, int64_t m,
+                                                             int32_t* __restrict__ cand, uint64_t* __restrict__ words,
+                                                             int strip, uint32_t* __restrict__ hist,
+                                                             unsigned* __restrict__ err) {
+  encode_words<MODE>(D, k, nrows, m, cand, words, nullptr, strip, hist, err);
 }
 
 // counts[d * ntiles + tile] = rows of the tile whose digit is d.
@@ -302,9 +334,12 @@ __global__ void __launch_bounds__(SORT_THREADS) k_sort_scatter(const uint64_t* _
 
 // n <= SORT_SMALL_MAX rows in one workgroup and one launch: for every word, encode through the
 // current permutation, find the digits that vary (OR xor AND over the rows), and run their stable
-// passes between two LDS pair buffers. out[0 .. m_out) = the first rows of the order.
-__global__ void __launch_bounds__(SORT_SMALL_THREADS) k_sort_small(SortDesc D, int32_t n, int32_t m_out,
-                                                             int32_t* __restrict__ out, unsigned* __restrict__ err) {
+// passes between two LDS pair buffers. out[0 .. m_out) = the first rows of the order. LIST (the
+// top-k's final sort): the rows are the n entries of `rows` (row indices below nrows, flag bit 31
+// ignored), not 0 .. n - 1 (nrows == n), and rows that compare equal keep the list's order.
+template <bool LIST>
+__device__ __forceinline__ void sort_small(const SortDesc& D, int32_t n, int32_t nrows, const int32_t* __restrict__ rows,
+                                           int32_t m_out, int32_t* __restrict__ out, unsigned* __restrict__ err) {
   __shared__ uint64_t s_word[2][SORT_SMALL_MAX];
   __shared__ int32_t s_idx[2][SORT_SMALL_MAX];
   constexpr int WAVES = SORT_SMALL_THREADS / 64;
@@ -314,80 +349,7 @@ __global__ void __launch_bounds__(SORT_SMALL_THREADS) k_sort_small(SortDesc D, i
   __shared__ uint64_t s_or[WAVES], s_and[WAVES];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   int cur = 0;
-  for (int p = threadIdx.x; p < n; p += SORT_SMALL_THREADS) s_idx[0][p] = p;
-  __syncthreads();
-  for (int k = 0; k < D.nwords; ++k) {
-    uint64_t o = 0, a = ~0ull;
-    for (int p = threadIdx.x; p < n; p += SORT_SMALL_THREADS) {
-      int32_t r = s_idx[cur][p];
-      if ((uint32_t)r >= (uint32_t)n) r = 0;
-      const uint64_t w = sort_word(D, r, k, err);
-      s_word[cur][p] = w;
-      o |= w;
-      a &= w;
-    }
-    for (int off = 32; off > 0; off >>= 1) {
-      o |= __shfl_xor(o, off);
-      a &= __shfl_xor(a, off);
-    }
-    if (lane == 0) {
-      s_or[wid] = o;
-      s_and[wid] = a;
-    }
-    __syncthreads();
-    o = 0;
-    a = ~0ull;
-#pragma unroll
-    for (int w = 0; w < WAVES; ++w) {
-      o |= s_or[w];
-      a &= s_and[w];
-    }
-    __syncthreads();
-    const uint64_t diff = o ^ a;  // bits that are not the same in every row (the same in every thread)
-    for (int g = 0; g < 8; ++g) {
-      if (((diff >> (8 * g)) & 255u) == 0) continue;
-      uint64_t w[SORT_SMALL_ITEMS];
-      int32_t ix[SORT_SMALL_ITEMS];
-      uint32_t dig[SORT_SMALL_ITEMS], pos[SORT_SMALL_ITEMS];
-#pragma unroll
-      for (int it = 0; it < SORT_SMALL_ITEMS; ++it) {
-        const int p = wid * (64 * SORT_SMALL_ITEMS) + it * 64 + lane;
-        const bool live = p < n;
-        w[it] = live ? s_word[cur][p] : ~0ull;
-        ix[it] = live ? s_idx[cur][p] : 0;
-        dig[it] = live ? (uint32_t)(w[it] >> (8 * g)) & 255u : 255u;
-      }
-      tile_rank<SORT_SMALL_THREADS, SORT_SMALL_ITEMS>(dig, pos, s_wcnt, s_dstart, s_wsum);
-#pragma unroll
-      for (int it = 0; it < SORT_SMALL_ITEMS; ++it) {
-        if (pos[it] < (uint32_t)SORT_SMALL_MAX) {
-          s_word[cur ^ 1][pos[it]] = w[it];
-          s_idx[cur ^ 1][pos[it]] = ix[it];
-        }
-      }
-      __syncthreads();
-      cur ^= 1;
-    }
-  }
-  for (int p = threadIdx.x; p < m_out; p += SORT_SMALL_THREADS) out[p] = s_idx[cur][p];
-}
-
-// k_sort_small over a row list (the top-k's final sort): the rows are the n entries of `rows` (row
-// indices below nrows, flag bit 31 ignored), not 0 .. n - 1, and rows that compare equal keep the
-// list's order. A kernel of its own, so that k_sort_small stays the kernel it was.
-__global__ void __launch_bounds__(SORT_SMALL_THREADS) k_sort_small_rows(SortDesc D, int32_t n, int32_t nrows,
-                                                                  const int32_t* __restrict__ rows, int32_t m_out,
-                                                                  int32_t* __restrict__ out, unsigned* __restrict__ err) {
-  __shared__ uint64_t s_word[2][SORT_SMALL_MAX];
-  __shared__ int32_t s_idx[2][SORT_SMALL_MAX];
-  constexpr int WAVES = SORT_SMALL_THREADS / 64;
-  __shared__ uint16_t s_wcnt[WAVES][256];
-  __shared__ uint32_t s_dstart[256];
-  __shared__ uint32_t s_wsum[4];
-  __shared__ uint64_t s_or[WAVES], s_and[WAVES];
-  const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
-  int cur = 0;
-  for (int p = threadIdx.x; p < n; p += SORT_SMALL_THREADS) s_idx[0][p] = rows[p] & 0x7FFFFFFF;
+  for (int p = threadIdx.x; p < n; p += SORT_SMALL_THREADS) s_idx[0][p] = LIST ? rows[p] & 0x7FFFFFFF : p;
   __syncthreads();
   for (int k = 0; k < D.nwords; ++k) {
     uint64_t o = 0, a = ~0ull;
@@ -445,48 +407,25 @@ __global__ void __launch_bounds__(SORT_SMALL_THREADS) k_sort_small_rows(SortDesc
   for (int p = threadIdx.x; p < m_out; p += SORT_SMALL_THREADS) out[p] = s_idx[cur][p];
 }
 
+__global__ void __launch_bounds__(SORT_SMALL_THREADS) k_sort_small(SortDesc D, int32_t n, int32_t m_out,
+                                                             int32_t* __restrict__ out, unsigned* __restrict__ err) {
+  sort_small<false>(D, n, n, nullptr, m_out, out, err);
+}
+
+__global__ void __launch_bounds__(SORT_SMALL_THREADS) k_sort_small_rows(SortDesc D, int32_t n, int32_t nrows,
+                                                                  const int32_t* __restrict__ rows, int32_t m_out,
+                                                                  int32_t* __restrict__ out, unsigned* __restrict__ err) {
+  sort_small<true>(D, n, nrows, rows, m_out, out, err);
+}
+
 // ---- top-k: radix selection (qe_topk_plan.hpp holds the host's rules) ------------------------------
 // The candidate list: row indices in ascending row order, bit 31 set on a sure row. A tied row's
 // current key word lies beside it; a sure row's word is never read again. Before the first
 // compaction the list is implicit: every row, all tied.
-constexpr uint32_t TOPK_SURE = 0x80000000u;
 constexpr int TOPK_THREADS = 256;
 constexpr int TOPK_ITEMS = 16;
 constexpr int TOPK_TILE = TOPK_THREADS * TOPK_ITEMS;  // candidates per workgroup of a compaction
 static_assert(TOPK_TILE == SORT_TILE, "qe_sort_layout reports one tile size");
-
-// Key words of list entries, and the 8 digit histograms of the rows it encodes.
-//   TW_ALL  : the implicit list, rows 0 .. m - 1; nothing but the histograms is written
-//   TW_TIED : word k of the tied entries of `cand` -> words[i]
-//   TW_SORT : word k of every entry of `cand` -> words[i]; `strip`: the flag bits leave `cand` (the
-//             final sort's first word: from here on the list is the sort's permutation)
-enum { TW_ALL = 0, TW_TIED = 1, TW_SORT = 2 };
-template <int MODE>
-__global__ void __launch_bounds__(ENC_THREADS) k_topk_words(SortDesc D, int64_t k, int64_t nrows, int64_t m,
-                                                             int32_t* __restrict__ cand, uint64_t* __restrict__ words,
-                                                             int strip, uint32_t* __restrict__ hist,
-                                                             unsigned* __restrict__ err) {
-  __shared__ uint32_t h[8 * 256];
-  for (int j = threadIdx.x; j < 8 * 256; j += ENC_THREADS) h[j] = 0;
-  __syncthreads();
-  for (int64_t i = blockIdx.x * (int64_t)ENC_THREADS + threadIdx.x; i < m; i += (int64_t)gridDim.x * ENC_THREADS) {
-    int64_t r = i;
-    if (MODE != TW_ALL) {
-      const uint32_t c = (uint32_t)cand[i];
-      if (MODE == TW_TIED && (c & TOPK_SURE)) continue;
-      r = (int64_t)(c & ~TOPK_SURE);
-      if (MODE == TW_SORT && strip) cand[i] = (int32_t)r;
-    }
-    if ((uint64_t)r >= (uint64_t)nrows) r = 0;  // (a candidate never is)
-    const uint64_t w = sort_word(D, r, k, err);
-    if (MODE != TW_ALL) words[i] = w;
-#pragma unroll
-    for (int g = 0; g < 8; ++g) hist_add(h + 256 * g, (uint32_t)(w >> (8 * g)) & 255u);
-  }
-  __syncthreads();
-  for (int j = threadIdx.x; j < 8 * 256; j += ENC_THREADS)
-    if (h[j]) atomicAdd(&hist[j], h[j]);
-}
 
 struct TopkStep {
   int64_t k;         // the key word in play
@@ -566,8 +505,7 @@ __global__ void __launch_bounds__(TOPK_THREADS) k_topk_compact(SortDesc D, TopkS
   __shared__ uint32_t s_ws[WAVES], s_wt[WAVES];
   const int lane = threadIdx.x & 63, wid = threadIdx.x >> 6;
   const uint64_t lt = (1ull << lane) - 1;
-  if (hist)
-    for (int j = threadIdx.x; j < 8 * 256; j += TOPK_THREADS) h[j] = 0;
+  if (hist) hist_clear<TOPK_THREADS>(h);
   const int64_t t0 = (int64_t)blockIdx.x * TOPK_TILE + wid * (64 * TOPK_ITEMS);
   uint64_t w[TOPK_ITEMS];
   int32_t row[TOPK_ITEMS];
@@ -618,95 +556,29 @@ __global__ void __launch_bounds__(TOPK_THREADS) k_topk_compact(SortDesc D, TopkS
   }
   if (hist) {
     __syncthreads();
-    for (int j = threadIdx.x; j < 8 * 256; j += TOPK_THREADS)
-      if (h[j]) atomicAdd(&hist[j], h[j]);
+    hist_flush<TOPK_THREADS>(h, hist);
   }
 }
 
-// ---- qe_take -----------------------------------------------------------------------------------
-constexpr int TAKE_MAX_COLS = 8;
-enum { TK_UTF8 = 0, TK_BOOL = -1 };
-
-struct TakeCol {
-  const void* in;
-  const uint8_t* in_valid;
-  void* out;            // TK_UTF8: int2 (source byte offset, length) per output row
-  uint32_t* out_valid;  // whole 32-bit words
-  int32_t width;        // 8, 4, 1, TK_UTF8 or TK_BOOL
-  int32_t pad;
-  const int32_t* in_offs;
-};
-
-struct TakeArgs {
-  TakeCol cols[TAKE_MAX_COLS];
-  int32_t ncols;
-};
-
-// A wave's 64 result bits -> the two 32-bit words of rows [64 c, 64 c + 64) (bitmaps hold nwords words).
-__device__ __forceinline__ void store_bits64(uint32_t* __restrict__ bm, int64_t c, int64_t nwords, uint64_t bits, int lane) {
-  if (lane == 0 && 2 * c < nwords) bm[2 * c] = (uint32_t)bits;
-  if (lane == 1 && 2 * c + 1 < nwords) bm[2 * c + 1] = (uint32_t)(bits >> 32);
+// ---- the multi-workgroup digit pass -----------------------------------------------------------------
+// One stable pass over n (word, index) pairs by the digit at `shift`: tile counts, their scan, the
+// scatter from (win, iin) to (wout, iout). wout NULL: the last pass, whose words nobody reads.
+// counts, offs: 256 tiles + 1 entries each.
+static int sort_digit_pass(qe_ctx* ctx, const uint64_t* win, const int32_t* iin, uint64_t* wout, int32_t* iout, int64_t n,
+                           int shift, int64_t* counts, int64_t* offs) {
+  const int64_t ntiles = (int64_t)div_up((uint64_t)n, SORT_TILE);
+  hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, win, n, shift, ntiles, counts);
+  QE_TRY(launch_check("k_sort_count"));
+  QE_TRY(exclusive_scan_i64(ctx, counts, offs, 256 * ntiles));
+  hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, win, iin, wout, iout, n, shift,
+                     ntiles, (const int64_t*)offs);
+  return launch_check("k_sort_scatter");
 }
 
-// Output row i = input row idx[i], one row per lane. An index outside [0, nin) reads nothing: the
-// row gets a zero value and a null bit, and *flag is set. OR_NULL (qe_take_or_null): index -1 means
-// "no row" and is written the same way without setting the flag.
-template <bool OR_NULL>
-__global__ void __launch_bounds__(256) k_take(const int32_t* __restrict__ idx, int64_t m, int64_t nin, TakeArgs A,
-                                              unsigned* __restrict__ flag) {
-  const int lane = threadIdx.x & 63;
-  const int64_t nchunks = (m + 63) >> 6, nwords = (m + 31) >> 5;
-  const int64_t wave = (blockIdx.x * (int64_t)blockDim.x + threadIdx.x) >> 6;
-  const int64_t nwaves = ((int64_t)gridDim.x * blockDim.x) >> 6;
-  for (int64_t c = wave; c < nchunks; c += nwaves) {  // the same trip count in every lane of a wave
-    const int64_t i = c * 64 + lane;
-    const bool live = i < m;
-    const int64_t r = live ? (int64_t)idx[i] : 0;
-    const bool ok = live && (uint64_t)r < (uint64_t)nin;
-    if (live && !ok && !(OR_NULL && r == -1)) *flag = 1u;
-    for (int k = 0; k < A.ncols; ++k) {
-      const TakeCol& C = A.cols[k];
-      if (C.width == 8) {
-        const uint64_t v = ok ? ((const uint64_t*)C.in)[r] : 0;
-        if (live) ((uint64_t*)C.out)[i] = v;
-      } else if (C.width == 4) {
-        const uint32_t v = ok ? ((const uint32_t*)C.in)[r] : 0;
-        if (live) ((uint32_t*)C.out)[i] = v;
-      } else if (C.width == 1) {
-        const uint8_t v = ok ? ((const uint8_t*)C.in)[r] : 0;
-        if (live) ((uint8_t*)C.out)[i] = v;
-      } else if (C.width == TK_UTF8) {
-        int2 e = make_int2(0, 0);
-        if (ok) {
-          e.x = C.in_offs[r];
-          e.y = max(C.in_offs[r + 1] - e.x, 0);
-        }
-        if (live) ((int2*)C.out)[i] = e;
-      } else {  // TK_BOOL
-        const bool b = ok && ((((const uint8_t*)C.in)[r >> 3] >> (r & 7)) & 1);
-        store_bits64((uint32_t*)C.out, c, nwords, __ballot(b), lane);
-      }
-      if (C.out_valid) {
-        const bool v = ok && (!C.in_valid || ((C.in_valid[r >> 3] >> (r & 7)) & 1));
-        store_bits64(C.out_valid, c, nwords, __ballot(v), lane);
-      }
-    }
-  }
-}
-
-struct DevBlock {  // working memory of one call: freed stream-ordered when the call returns
-  qe_ctx* ctx;
-  void* p = nullptr;
-  explicit DevBlock(qe_ctx* c) : ctx(c) {}
-  ~DevBlock() { dev_free(ctx, p); }
-};
-
-inline size_t align256(size_t x) { return (x + 255) & ~size_t(255); }
-
-// The multi-workgroup passes for other translation units (qe_join.hip orders build rows by slot):
-// a stable sort of n (word, index) pairs by the low `bits` bits of the words, between the two
-// buffers of each kind, starting in buffer 0. *cur = the buffer that holds the sorted indices (the
-// words of the last pass are not written). `scratch`: sort_pairs_scratch_bytes(n) bytes.
+// The passes for other translation units (qe_join.hip orders build rows by slot): a stable sort of
+// n (word, index) pairs by the low `bits` bits of the words, between the two buffers of each kind,
+// starting in buffer 0. *cur = the buffer that holds the sorted indices (the words of the last pass
+// are not written). `scratch`: sort_pairs_scratch_bytes(n) bytes.
 size_t sort_pairs_scratch_bytes(int64_t n) {
   const int64_t ntiles = (int64_t)div_up((uint64_t)std::max<int64_t>(n, 1), SORT_TILE);
   return 2 * align256((size_t)(256 * ntiles + 1) * 8);
@@ -715,19 +587,12 @@ size_t sort_pairs_scratch_bytes(int64_t n) {
 int sort_pairs(qe_ctx* ctx, uint64_t* const words[2], int32_t* const idx[2], int64_t n, int bits, void* scratch, int* cur) {
   *cur = 0;
   if (n <= 0) return QE_OK;
-  const int64_t ntiles = (int64_t)div_up((uint64_t)n, SORT_TILE);
   int64_t* d_counts = (int64_t*)scratch;
   int64_t* d_offs = (int64_t*)((char*)scratch + sort_pairs_scratch_bytes(n) / 2);
   const int nd = (bits + 7) / 8;
   for (int j = 0; j < nd; ++j) {
-    const int shift = 8 * j, c = *cur;
-    hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, words[c], n, shift, ntiles,
-                       d_counts);
-    QE_TRY(launch_check("k_sort_count"));
-    QE_TRY(exclusive_scan_i64(ctx, d_counts, d_offs, 256 * ntiles));
-    hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, words[c], idx[c],
-                       j + 1 < nd ? words[c ^ 1] : (uint64_t*)nullptr, idx[c ^ 1], n, shift, ntiles, d_offs);
-    QE_TRY(launch_check("k_sort_scatter"));
+    const int c = *cur;
+    QE_TRY(sort_digit_pass(ctx, words[c], idx[c], j + 1 < nd ? words[c ^ 1] : nullptr, idx[c ^ 1], n, 8 * j, d_counts, d_offs));
     *cur = c ^ 1;
   }
   return QE_OK;
@@ -784,21 +649,27 @@ struct SortMem {
   int64_t readbacks = 0;
 };
 
-// rows: entries of each pair buffer; cnt: entries of each of the two counter arrays (0: none).
-static int sort_mem(qe_ctx* ctx, DevBlock& blk, int64_t rows, int64_t cnt, SortMem* M) {
-  const size_t words_b = rows ? align256((size_t)rows * 8) : 0, idx_b = rows ? align256((size_t)rows * 4) : 0;
-  const size_t cnt_b = cnt ? align256((size_t)cnt * 8) : 0;
-  QE_TRY(dev_alloc(ctx, SORT_HEAD + SORT_HIST_B + 2 * words_b + 2 * idx_b + 2 * cnt_b, &blk.p));
-  char* base = (char*)blk.p;
-  M->base = base;
-  M->err = (unsigned*)base;
-  M->hist = (uint32_t*)(base + SORT_HEAD);
-  char* p = base + SORT_HEAD + SORT_HIST_B;
+// The two word and two index buffers of `rows` entries each (0: none): their bytes, and their places
+// from p on; returns the first byte behind them.
+static size_t pairs_bytes(int64_t rows) { return 2 * align256((size_t)rows * 8) + 2 * align256((size_t)rows * 4); }
+static char* carve_pairs(char* p, int64_t rows, SortMem* M) {
+  const size_t words_b = align256((size_t)rows * 8), idx_b = align256((size_t)rows * 4);
   M->words[0] = (uint64_t*)p;
   M->words[1] = (uint64_t*)(p + words_b);
   M->idx[0] = (int32_t*)(p + 2 * words_b);
   M->idx[1] = (int32_t*)(p + 2 * words_b + idx_b);
-  M->counts = (int64_t*)(p + 2 * words_b + 2 * idx_b);
+  return p + 2 * words_b + 2 * idx_b;
+}
+
+// rows: entries of each pair buffer; cnt: entries of each of the two counter arrays (0: none).
+static int sort_mem(qe_ctx* ctx, Blocks& blk, int64_t rows, int64_t cnt, SortMem* M) {
+  const size_t cnt_b = align256((size_t)cnt * 8);
+  char* base;
+  QE_TRY(blk.alloc(SORT_HEAD + SORT_HIST_B + pairs_bytes(rows) + 2 * cnt_b, (void**)&base));
+  M->base = base;
+  M->err = (unsigned*)base;
+  M->hist = (uint32_t*)(base + SORT_HEAD);
+  M->counts = (int64_t*)carve_pairs(base + SORT_HEAD + SORT_HIST_B, rows, M);
   M->offs = (int64_t*)((char*)M->counts + cnt_b);
   QE_HIP(hipMemsetAsync(base, 0, SORT_HEAD, ctx->stream));
   QE_TRY(ctx_pinned(ctx, SORT_HEAD + SORT_HIST_B, &M->hp));
@@ -829,8 +700,7 @@ static int sort_build_desc(qe_ctx* ctx, const qe_column* keys, const int32_t* fl
       promised = true;
       continue;
     }
-    const int grid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)n, 256), (int64_t)ctx->num_cus * 8);
-    hipLaunchKernelGGL(k_utf8_max_len, dim3(grid), dim3(256), 0, ctx->stream, keys[q].offsets, n,
+    hipLaunchKernelGGL(k_utf8_max_len, dim3(stride_grid(ctx, n)), dim3(256), 0, ctx->stream, keys[q].offsets, n,
                        (int32_t*)M.base + 4 + 4 * q);
     QE_TRY(launch_check("k_utf8_max_len"));
     reduced = true;
@@ -891,8 +761,7 @@ static int sort_build_desc(qe_ctx* ctx, const qe_column* keys, const int32_t* fl
 // the index buffer that holds the order.
 static int sort_multi(qe_ctx* ctx, const SortDesc& D, int64_t nrows, int64_t m, bool list, SortMem& M, int cur,
                       int* cur_out) {
-  const int64_t ntiles = (int64_t)div_up((uint64_t)m, SORT_TILE);
-  const int egrid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)m, ENC_THREADS), (int64_t)ctx->num_cus * 8);
+  const int egrid = stride_grid(ctx, m, ENC_THREADS);
   for (int64_t k = 0; k < D.nwords; ++k) {
     QE_HIP(hipMemsetAsync(M.hist, 0, SORT_HIST_B, ctx->stream));
     if (list) {
@@ -912,18 +781,9 @@ static int sort_multi(qe_ctx* ctx, const SortDesc& D, int64_t nrows, int64_t m, 
       for (int v = 0; v < 256; ++v) constant |= M.h_hist[256 * g + v] == (uint32_t)m;
       if (!constant) digits[nd++] = g;
     }
-    for (int j = 0; j < nd; ++j) {
-      const int shift = 8 * digits[j];
-      hipLaunchKernelGGL(k_sort_count, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, M.words[cur], m, shift,
-                         ntiles, M.counts);
-      QE_TRY(launch_check("k_sort_count"));
-      QE_TRY(exclusive_scan_i64(ctx, M.counts, M.offs, 256 * ntiles));
-      hipLaunchKernelGGL(k_sort_scatter, dim3((unsigned)ntiles), dim3(SORT_THREADS), 0, ctx->stream, M.words[cur],
-                         M.idx[cur], j + 1 < nd ? M.words[cur ^ 1] : (uint64_t*)nullptr, M.idx[cur ^ 1], m, shift, ntiles,
-                         M.offs);
-      QE_TRY(launch_check("k_sort_scatter"));
-      cur ^= 1;
-    }
+    for (int j = 0; j < nd; ++j, cur ^= 1)
+      QE_TRY(sort_digit_pass(ctx, M.words[cur], M.idx[cur], j + 1 < nd ? M.words[cur ^ 1] : nullptr, M.idx[cur ^ 1], m,
+                             8 * digits[j], M.counts, M.offs));
   }
   *cur_out = cur;
   return QE_OK;
@@ -941,7 +801,7 @@ static int sort_impl(qe_ctx* ctx, const char* who, const qe_column* keys, const 
 
   const bool small = n <= SORT_SMALL_MAX;
   const int64_t ntiles = (int64_t)div_up((uint64_t)n, SORT_TILE);
-  DevBlock blk(ctx);
+  Blocks blk(ctx);
   SortMem M;
   M.who = who;
   QE_TRY(sort_mem(ctx, blk, small ? 0 : n, small ? 0 : 256 * ntiles + 1, &M));
@@ -965,14 +825,10 @@ static int sort_impl(qe_ctx* ctx, const char* who, const qe_column* keys, const 
 
 // The top-k's two (word, index) candidate buffers of `rows` entries each, in a block of their own:
 // they are sized once the first pick has bounded the candidates, after the block of sort_mem.
-static int topk_mem_pairs(qe_ctx* ctx, DevBlock& blk, int64_t rows, SortMem* M) {
-  const size_t words_b = align256((size_t)rows * 8), idx_b = align256((size_t)rows * 4);
-  QE_TRY(dev_alloc(ctx, 2 * words_b + 2 * idx_b, &blk.p));
-  char* p = (char*)blk.p;
-  M->words[0] = (uint64_t*)p;
-  M->words[1] = (uint64_t*)(p + words_b);
-  M->idx[0] = (int32_t*)(p + 2 * words_b);
-  M->idx[1] = (int32_t*)(p + 2 * words_b + idx_b);
+static int topk_mem_pairs(Blocks& blk, int64_t rows, SortMem* M) {
+  char* p;
+  QE_TRY(blk.alloc(pairs_bytes(rows), (void**)&p));
+  carve_pairs(p, rows, M);
   return QE_OK;
 }
 
@@ -980,7 +836,7 @@ static int topk_mem_pairs(qe_ctx* ctx, DevBlock& blk, int64_t rows, SortMem* M) 
 // M.words[cur] (implicit: over all n rows, and nothing else is written), read back.
 static int topk_histogram(qe_ctx* ctx, const SortDesc& D, int64_t kw, int64_t n, bool implicit, int64_t cand, SortMem& M,
                           int cur) {
-  const int egrid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)cand, ENC_THREADS), (int64_t)ctx->num_cus * 8);
+  const int egrid = stride_grid(ctx, cand, ENC_THREADS);
   QE_HIP(hipMemsetAsync(M.hist, 0, SORT_HIST_B, ctx->stream));
   if (implicit)
     hipLaunchKernelGGL(k_topk_words<TW_ALL>, dim3(egrid), dim3(ENC_THREADS), 0, ctx->stream, D, kw, n, n, (int32_t*)nullptr,
@@ -1031,7 +887,7 @@ static int topk_select(qe_ctx* ctx, const qe_column* keys, const int32_t* flags,
   const int64_t cnt = n <= SORT_SMALL_MAX ? 0
                                           : std::max<int64_t>(2 * (int64_t)div_up((uint64_t)n, TOPK_TILE) + 1,
                                                               256 * (int64_t)div_up((uint64_t)fmax, SORT_TILE) + 1);
-  DevBlock blk(ctx), pairs(ctx);
+  Blocks blk(ctx);
   QE_TRY(sort_mem(ctx, blk, 0, cnt, &M));
   SortDesc D;
   bool promised;
@@ -1067,7 +923,7 @@ static int topk_select(qe_ctx* ctx, const qe_column* keys, const int32_t* flags,
       C.cut();
     }
     have_hist = g >= 0 && !topk_stop(C.candidates(), m, SORT_SMALL_MAX);  // another step follows: it needs histograms
-    if (implicit) QE_TRY(topk_mem_pairs(ctx, pairs, C.candidates(), &M));
+    if (implicit) QE_TRY(topk_mem_pairs(blk, C.candidates(), &M));
     QE_TRY(topk_compact(ctx, D, S, implicit, before, C.candidates(), M, cur, have_hist));
     if (!implicit) cur ^= 1;
     implicit = false;
@@ -1086,7 +942,7 @@ static int topk_select(qe_ctx* ctx, const qe_column* keys, const int32_t* flags,
     if (promised) QE_TRY(sort_read_back(ctx, M, 4));
     return QE_OK;
   }
-  if (implicit) QE_TRY(topk_mem_pairs(ctx, pairs, n, &M));  // no step ran: the candidates are all n rows
+  if (implicit) QE_TRY(topk_mem_pairs(blk, n, &M));  // no step ran: the candidates are all n rows
   QE_TRY(sort_multi(ctx, D, n, cand, !implicit, M, cur, &cur));
   QE_HIP(hipMemcpyAsync(out, M.idx[cur], (size_t)m * 4, hipMemcpyDeviceToDevice, ctx->stream));
   return QE_OK;
@@ -1139,120 +995,6 @@ int qe_topk_last_stats(qe_ctx* ctx, int64_t stats[4]) {
   QE_CHECK(stats != nullptr, QE_ERR_INVALID_ARG, "topk: null stats");
   for (int i = 0; i < 4; ++i) stats[i] = ctx->topk_stats[i];
   return QE_OK;
-}
-
-}  // extern "C"
-
-// qe_take, and qe_take_or_null (or_null: index -1 is "no row", and every output needs a validity buffer).
-static int take_impl(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int32_t ncols, qe_column* outs,
-                     const int64_t* utf8_capacity, bool or_null) {
-  QE_TRY(ctx_enter(ctx));
-  QE_CHECK(indices != nullptr, QE_ERR_INVALID_ARG, "take: null indices");
-  QE_CHECK(indices->type == QE_TYPE_INT32 && !indices->validity, QE_ERR_INVALID_ARG,
-           "take: the indices column must be INT32 without validity");
-  QE_CHECK(ncols >= 0 && ncols <= TAKE_MAX_COLS, QE_ERR_UNSUPPORTED, "take: at most %d columns per call", TAKE_MAX_COLS);
-  QE_CHECK(ncols == 0 || (inputs && outs), QE_ERR_INVALID_ARG, "take: null column arrays");
-  const int64_t m = indices->length;
-  QE_CHECK(m >= 0 && (indices->values || m == 0), QE_ERR_INVALID_ARG, "take: the indices column has no values");
-  const int64_t nin = ncols ? inputs[0].length : 0;
-  TakeArgs args{};
-  args.ncols = ncols;
-  int nutf8 = 0;
-  for (int i = 0; i < ncols; ++i) {
-    const qe_column& in = inputs[i];
-    const qe_column& out = outs[i];
-    const bool utf8 = in.type == QE_TYPE_UTF8, boolean = in.type == QE_TYPE_BOOL;
-    QE_CHECK(is_fixed(in.type) || utf8 || boolean, QE_ERR_UNSUPPORTED, "take: column %d type %d not supported", i, in.type);
-    QE_CHECK(in.length == nin && nin >= 0, QE_ERR_INVALID_ARG, "take: column %d has %lld rows, column 0 %lld", i,
-             (long long)in.length, (long long)nin);
-    QE_CHECK(in.values || nin == 0, QE_ERR_INVALID_ARG, "take: column %d has no values", i);
-    QE_CHECK(out.type == in.type && (out.values || m == 0), QE_ERR_INVALID_ARG, "take: output %d must have the input's type", i);
-    QE_CHECK(out.length >= m, QE_ERR_CAPACITY, "take: output %d holds %lld rows, need %lld", i, (long long)out.length,
-             (long long)m);
-    QE_CHECK((!in.validity || out.validity) && ((uintptr_t)out.validity & 3) == 0, QE_ERR_INVALID_ARG,
-             "take: output %d needs a 4-byte aligned validity buffer", i);
-    QE_CHECK(!or_null || out.validity, QE_ERR_INVALID_ARG, "take: output %d needs a validity buffer (index -1 gives a null row)", i);
-    QE_CHECK(!boolean || ((uintptr_t)out.values & 3) == 0, QE_ERR_INVALID_ARG, "take: BOOL output %d must be 4-byte aligned", i);
-    QE_CHECK(!utf8 || ((in.offsets || nin == 0) && out.offsets), QE_ERR_INVALID_ARG, "take: UTF8 column %d needs offsets", i);
-    QE_CHECK(!utf8 || (utf8_capacity && utf8_capacity[i] >= 0), QE_ERR_INVALID_ARG,
-             "take: UTF8 output %d needs its values capacity (utf8_capacity)", i);
-    args.cols[i] = TakeCol{in.values, in.validity, out.values, out.validity ? (uint32_t*)out.validity : nullptr,
-                           utf8 ? TK_UTF8 : boolean ? TK_BOOL : type_width(in.type), 0, utf8 ? in.offsets : nullptr};
-    // an output validity buffer without an input one is filled too: all valid, nulls for bad indices
-    nutf8 += utf8;
-  }
-  if (m == 0) {
-    for (int i = 0; i < ncols; ++i) {
-      if (inputs[i].type == QE_TYPE_UTF8) QE_HIP(hipMemsetAsync(outs[i].offsets, 0, 4, ctx->stream));
-      outs[i].length = 0;
-    }
-    return QE_OK;
-  }
-  // working memory: [flag | per UTF8 column: (start, length) pairs, tile sums and offsets]
-  const int64_t stiles = utf8_gather_tiles(m);
-  const size_t pairs_b = align256((size_t)m * sizeof(int2)), tsum_b = align256((size_t)(2 * stiles + 1) * 8);
-  DevBlock blk(ctx);
-  QE_TRY(dev_alloc(ctx, 256 + (size_t)nutf8 * (pairs_b + tsum_b), &blk.p));
-  char* base = (char*)blk.p;
-  unsigned* d_flag = (unsigned*)base;
-  QE_HIP(hipMemsetAsync(d_flag, 0, 4, ctx->stream));
-  const int2* pairs[TAKE_MAX_COLS] = {};
-  int64_t* tsum[TAKE_MAX_COLS] = {};
-  for (int i = 0, u = 0; i < ncols; ++i) {
-    if (args.cols[i].width != TK_UTF8) continue;
-    char* p = base + 256 + (size_t)u++ * (pairs_b + tsum_b);
-    pairs[i] = (const int2*)p;
-    tsum[i] = (int64_t*)(p + pairs_b);
-    args.cols[i].out = p;
-  }
-  if (ncols > 0) {
-    const int grid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)m, 256), (int64_t)ctx->num_cus * 8);
-    if (or_null)
-      hipLaunchKernelGGL(k_take<true>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t*)indices->values, m, nin, args,
-                         d_flag);
-    else
-      hipLaunchKernelGGL(k_take<false>, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t*)indices->values, m, nin, args,
-                         d_flag);
-    QE_TRY(launch_check("k_take"));
-  }
-  // the flag and the UTF8 byte totals come back together, before any byte is copied
-  void* hp;
-  QE_TRY(ctx_pinned(ctx, 8 * (1 + TAKE_MAX_COLS), &hp));
-  int64_t* h = (int64_t*)hp;
-  QE_HIP(hipMemcpyAsync(h, d_flag, 4, hipMemcpyDeviceToHost, ctx->stream));
-  for (int i = 0; i < ncols; ++i) {
-    if (!pairs[i]) continue;
-    QE_TRY(utf8_gather_lengths(ctx, pairs[i], m, tsum[i]));
-    QE_HIP(hipMemcpyAsync(h + 1 + i, tsum[i] + 2 * stiles, 8, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  QE_TRY(ctx_sync(ctx));
-  QE_CHECK(*(const unsigned*)h == 0, QE_ERR_INVALID_ARG,
-           "take: an index is outside [0, %lld) (its row was written as null / zero)", (long long)nin);
-  for (int i = 0; i < ncols; ++i) {
-    if (!pairs[i]) continue;
-    QE_CHECK(h[1 + i] < ((int64_t)1 << 31), QE_ERR_UNSUPPORTED, "take: UTF8 output %d needs %lld bytes (int32 offsets)", i,
-             (long long)h[1 + i]);
-    QE_CHECK(h[1 + i] <= utf8_capacity[i], QE_ERR_CAPACITY, "take: UTF8 output %d holds %lld bytes, need %lld", i,
-             (long long)utf8_capacity[i], (long long)h[1 + i]);
-  }
-  for (int i = 0; i < ncols; ++i)
-    if (pairs[i])
-      QE_TRY(utf8_gather_copy(ctx, pairs[i], m, tsum[i], (const uint8_t*)inputs[i].values, outs[i].offsets,
-                              (uint8_t*)outs[i].values));
-  for (int i = 0; i < ncols; ++i) outs[i].length = m;
-  return QE_OK;
-}
-
-extern "C" {
-
-int qe_take(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int32_t ncols, qe_column* outs,
-            const int64_t* utf8_capacity) {
-  return take_impl(ctx, indices, inputs, ncols, outs, utf8_capacity, false);
-}
-
-int qe_take_or_null(qe_ctx* ctx, const qe_column* indices, const qe_column* inputs, int32_t ncols, qe_column* outs,
-                    const int64_t* utf8_capacity) {
-  return take_impl(ctx, indices, inputs, ncols, outs, utf8_capacity, true);
 }
 
 }  // extern "C"

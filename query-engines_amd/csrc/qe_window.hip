@@ -31,7 +31,7 @@
 // An `order` entry outside [0, n) is never used as an index: its position gathers a null, the inverse
 // permutation keeps -1 for the rows no position names (their results are null / 0), and a device flag
 // fails the call.
-#include "qe_internal.hpp"
+#include "qe_rows.hpp"
 #include "qe_window_plan.hpp"
 
 namespace qe {
@@ -104,8 +104,6 @@ __device__ __forceinline__ uint32_t win_word(const uint32_t* __restrict__ bm, in
   if (w == 0) x |= 1u;
   return x;
 }
-
-__device__ __forceinline__ bool win_valid(const uint8_t* __restrict__ v, int64_t r) { return !v || ((v[r >> 3] >> (r & 7)) & 1); }
 
 // Row r of a fixed-width column as int64: integers by value, FLOAT64 its bits (0 for other types,
 // whose values COUNT never reads).
@@ -188,7 +186,7 @@ __device__ __forceinline__ WinElem win_load(const WinJob& J, const WinCommon& C,
     default: break;
   }
   const int64_t r = C.order[k];
-  const bool valid = (uint64_t)r < (uint64_t)C.n && win_valid(J.in_valid, r);
+  const bool valid = (uint64_t)r < (uint64_t)C.n && row_valid(J.in_valid, r);
   const int64_t v = valid ? win_value(J.in_type, J.in, r) : 0;
   if (J.src == WS_SUM) {
     e.v = v;
@@ -288,12 +286,6 @@ __device__ __forceinline__ WinElem win_scan_tile(const WinJob& J, const WinCommo
 }
 
 // ---- evaluate ---------------------------------------------------------------------------------------
-// A wave's 64 result bits -> the two 32-bit words of rows [64 c, 64 c + 64) (bitmaps hold nwords words).
-__device__ __forceinline__ void win_store_bits64(uint32_t* __restrict__ bm, int64_t c, int64_t nwords, uint64_t bits, int lane) {
-  if (lane == 0 && 2 * c < nwords) bm[2 * c] = (uint32_t)bits;
-  if (lane == 1 && 2 * c + 1 < nwords) bm[2 * c + 1] = (uint32_t)(bits >> 32);
-}
-
 __device__ __forceinline__ uint32_t win_mask_le(int64_t i) { return 0xFFFFFFFFu >> (31 - (int)(i & 31)); }
 
 // Every function at sorted position i (i < n), into the record `rec`: A.nfns values, then one word of
@@ -352,7 +344,7 @@ __device__ __forceinline__ void win_eval_pos(const WinArgs& A, int64_t i, int64_
         valid = false;
         if (inside) {
           const int64_t rr = C.order[F.fn == QE_WIN_LAG ? i - F.offset : i + F.offset];
-          if ((uint64_t)rr < (uint64_t)n && win_valid(F.in_valid, rr)) {
+          if ((uint64_t)rr < (uint64_t)n && row_valid(F.in_valid, rr)) {
             valid = true;
             val = win_value(F.in_type, F.in, rr);
           }
@@ -420,7 +412,7 @@ __device__ __forceinline__ void win_emit_block(const WinArgs& A, int64_t r0, Win
       else if (F.out_width == 4) ((int32_t*)F.out)[r] = (int32_t)val;
       else ((uint8_t*)F.out)[r] = (uint8_t)val;
     }
-    if (F.out_valid) win_store_bits64(F.out_valid, c, nwords, __ballot((valid_bits >> k) & 1), lane);
+    if (F.out_valid) store_bits64(F.out_valid, c, nwords, __ballot((valid_bits >> k) & 1), lane);
   }
   __syncthreads();  // L is rewritten by the next block of rows
 }
@@ -530,7 +522,7 @@ struct WinKeys {
 __device__ __forceinline__ bool win_rows_differ(const WinKeys& K, int64_t a, int64_t b) {
   for (int q = 0; q < K.n; ++q) {
     const WinKey& k = K.k[q];
-    const bool va = win_valid(k.valid, a), vb = win_valid(k.valid, b);
+    const bool va = row_valid(k.valid, a), vb = row_valid(k.valid, b);
     if (va != vb) return true;
     if (!va) continue;
     switch (k.type) {
@@ -586,16 +578,9 @@ __global__ void __launch_bounds__(256) k_win_boundaries(const int32_t* __restric
         start = (uint64_t)a >= (uint64_t)n || (uint64_t)b >= (uint64_t)n || win_rows_differ(K, a, b);
       }
     }
-    win_store_bits64(out, c, nwords, __ballot(start), lane);
+    store_bits64(out, c, nwords, __ballot(start), lane);
   }
 }
-
-struct WinBlock {  // working memory of one call: freed stream-ordered when the call returns
-  qe_ctx* ctx;
-  void* p = nullptr;
-  explicit WinBlock(qe_ctx* c) : ctx(c) {}
-  ~WinBlock() { dev_free(ctx, p); }
-};
 
 int check_order(const char* who, const qe_column* order, int64_t n) {
   QE_CHECK(order != nullptr, QE_ERR_INVALID_ARG, "%s: null order column", who);
@@ -657,8 +642,7 @@ int qe_window_boundaries(qe_ctx* ctx, const qe_column* keys, int32_t nkeys, cons
            "window_boundaries: the output needs a 4-byte aligned values buffer");
   starts->length = n;
   if (n == 0) return QE_OK;
-  const int grid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)n, 256), (int64_t)ctx->num_cus * 8);
-  hipLaunchKernelGGL(k_win_boundaries, dim3(grid), dim3(256), 0, ctx->stream, (const int32_t*)order->values, n, K,
+  hipLaunchKernelGGL(k_win_boundaries, dim3(stride_grid(ctx, n)), dim3(256), 0, ctx->stream, (const int32_t*)order->values, n, K,
                      (uint32_t*)starts->values);
   return launch_check("k_win_boundaries");
 }
@@ -715,9 +699,9 @@ int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_st
 
   const WindowScans S = window_scans(fns, nfns);
   const int64_t nw = window_words(n), tiles = window_tiles(n);
-  WinBlock blk(ctx);
-  QE_TRY(dev_alloc(ctx, (size_t)window_work_bytes(n, S.n, nfns), &blk.p));
-  char* p = (char*)blk.p;
+  Blocks blk(ctx);
+  char* p;
+  QE_TRY(blk.alloc((size_t)window_work_bytes(n, S.n, nfns), (void**)&p));
   A.c = WinCommon{(const int32_t*)order->values, (const uint32_t*)part_starts->values, (const uint32_t*)peer_starts->values, n, nw,
                   nullptr, (unsigned*)p};
   p += WIN_HEAD_BYTES;
@@ -762,7 +746,7 @@ int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_st
   } else {
     QE_HIP(hipMemsetAsync(A.c.flag, 0, 4, ctx->stream));
     QE_HIP(hipMemsetAsync(A.c.inv, 0xFF, (size_t)n * 4, ctx->stream));
-    const int grid = (int)std::min<int64_t>((int64_t)div_up((uint64_t)n, 256), (int64_t)ctx->num_cus * 8);
+    const int grid = stride_grid(ctx, n);
     hipLaunchKernelGGL(k_win_inverse, dim3(grid), dim3(256), 0, ctx->stream, A.c);
     QE_TRY(launch_check("k_win_inverse"));
     hipLaunchKernelGGL(k_win_reduce, dim3((unsigned)tiles, (unsigned)A.njobs), dim3(WIN_THREADS), 0, ctx->stream, A);

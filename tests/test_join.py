@@ -7,8 +7,8 @@ import pytest
 import joinref as R
 from kquery import native as N
 from kquery.columnar import Context, DeviceColumn, Field, RecordBatch, Schema
-from kquery.operators import (HashJoinExec, PhysicalPlan, join_build, join_probe, join_probe_mask, join_stats, take,
-                              take_or_null)
+from kquery.operators import (HashJoinExec, PhysicalPlan, join_build, join_probe, join_probe_mask, join_stats, sort_layout,
+                              take, take_or_null)
 
 pytestmark = pytest.mark.gpu
 
@@ -184,6 +184,18 @@ def test_big_duplicate_build_side(gpu_ctx):
     build = (N.TYPE_INT64, bv, rng.random(200_003) >= 0.1)
     pv = np.concatenate([bv[rng.integers(0, 200_003, 3000)], rng.integers(0, 1 << 62, 1097)])
     check(gpu_ctx, build, [(N.TYPE_INT64, pv, rng.random(4097) >= 0.1)], unique=False)
+
+
+def test_duplicate_build_side_one_row_past_a_tile(gpu_ctx):
+    """The ordering passes with a last tile of one row (T + 1 and 2 T + 1 build rows, three rows per key on
+    average), over slot words whose bit count is no multiple of the 8-bit digit."""
+    T, _ = sort_layout()
+    for nb in (T + 1, 2 * T + 1):
+        rng = np.random.default_rng(610 + nb)
+        bv = (rng.integers(0, nb // 3, nb).astype(np.uint64) * np.uint64(0x9E3779B97F4A7C15)).view(np.int64)
+        pv = np.concatenate([bv[rng.integers(0, nb, 500)], rng.integers(0, 1 << 62, 141)])
+        stats = check(gpu_ctx, (N.TYPE_INT64, bv, rng.random(nb) >= 0.1), [(N.TYPE_INT64, pv, rng.random(641) >= 0.1)], unique=False)
+        assert (stats[3] + 1).bit_length() % 8 != 0  # the passes sort by the bits of slots + 1
 
 
 # ---- edge keys ---------------------------------------------------------------------------------------------

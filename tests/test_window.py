@@ -268,6 +268,17 @@ def test_boundaries_no_key_and_second_key_only(gpu_ctx, layout):
         assert np.array_equal(starts_of(gpu_ctx, cols[:1], perm, n), W.starts([first], [0], np.arange(n)))
 
 
+def test_boundaries_around_one_bitmap_word(gpu_ctx):
+    """A wave writes two 32-bit words: row counts that end just before, at and just after the first of
+    them, and just after the second (a nullable key, so the validity bit is read too)."""
+    rng = np.random.default_rng(33)
+    for n in (31, 32, 33, 65):
+        key = (N.TYPE_INT64, _typed(N.TYPE_INT64, rng.integers(0, 3, n), False), rng.random(n) >= 0.2)
+        perm = np.arange(n, dtype=np.int32)
+        got = starts_of(gpu_ctx, [to_device(gpu_ctx, key)], DeviceColumn.from_numpy(N.TYPE_INT32, perm, ctx=gpu_ctx), n)
+        assert np.array_equal(got, W.starts([key], [0], perm)), n
+
+
 # ---- refusals -------------------------------------------------------------------------------------------
 def _filled(ctx, t, n, nullable):
     """An output column whose buffers hold a pattern no kernel writes."""
