@@ -387,9 +387,19 @@ int qe_window_layout(int32_t* tile_rows, int32_t* small_max);
  * max(64, 2 x non-null build rows); a key's home slot is fmix64(key word) & (slots - 1), fmix64 the
  * murmur3 64-bit finaliser. Every 64-bit value is a legal key.
  * Order: pairs come sorted by probe row and, within a probe row, by ascending build row: one
- * sequence, bit-identical from run to run, whatever slot a key landed in. */
+ * sequence, bit-identical from run to run, whatever slot a key landed in.
+ * Match marks (RIGHT / FULL OUTER joins and the semi / anti joins that keep build rows): a table
+ * carries one mark per distinct build key, all clear after qe_join_build. A tracked probe
+ * (QE_JOIN_TRACK) and qe_join_mark set the mark of every key that at least one of their non-null
+ * probe rows equals; marks accumulate over calls and setting one twice changes nothing. A build row
+ * is MATCHED iff its key is non-null and its key's mark is set: a null-key build row is never
+ * matched. A call that fails (QE_ERR_CAPACITY, QE_ERR_UNSUPPORTED, an argument error) leaves the
+ * marks as they were; an untracked probe and qe_join_probe_mask never touch them. The marks are
+ * slots + 1 bits, allocated by the first call that sets one: a table never tracked holds nothing
+ * more than its slots and runs. */
 #define QE_JOIN_INNER 0
 #define QE_JOIN_LEFT  1   /* probe-side outer: an unmatched probe row pairs with build index -1 */
+#define QE_JOIN_TRACK 0x100 /* OR-ed into INNER / LEFT: the same pairs, and the matched keys are marked */
 typedef struct qe_join qe_join;
 
 /* Builds the table over key->length <= 2^31-1 rows (zero rows or all nulls: a valid, empty table).
@@ -403,9 +413,26 @@ int qe_join_destroy(qe_join* j);
  * pair count; if the capacity is short nothing is written and the call returns QE_ERR_CAPACITY (call
  * again with *pairs rows). A table whose keys are unique (qe_join_stats max_dup == 1) never needs
  * more than key->length rows. More than 2^31-1 pairs: QE_ERR_UNSUPPORTED. QE_JOIN_LEFT emits
- * exactly one pair (i, -1) for an unmatched or null-key probe row i. One read-back (the count). */
+ * exactly one pair (i, -1) for an unmatched or null-key probe row i. One read-back (the count).
+ * kind: QE_JOIN_INNER or QE_JOIN_LEFT, alone or OR-ed with QE_JOIN_TRACK; any other bit or value:
+ * QE_ERR_INVALID_ARG. A tracked call writes exactly the untracked kind's pairs and, once it has
+ * succeeded, has marked every build key it matched (the -1 pair of a LEFT row marks nothing). */
 int qe_join_probe(qe_join* j, const qe_column* key, int32_t kind,
                   qe_column* probe_idx, qe_column* build_idx, int64_t* pairs);
+/* Marks the build keys that `key`'s non-null rows equal and writes nothing else: the marking of a
+ * tracked probe without its pairs. The same key checks as a probe; 0 rows: nothing happens.
+ * Stream-ordered, no host wait. */
+int qe_join_mark(qe_join* j, const qe_column* key);
+/* The build rows that are matched (matched != 0) or unmatched (matched == 0: every null-key row is
+ * among them), as ascending row indices, bit-identical from run to run. idx: INT32 without validity;
+ * its length on entry is the row capacity and is set on return. *rows always receives the exact
+ * count; if the capacity is short nothing is written and the call returns QE_ERR_CAPACITY (the build
+ * side's total row count, null rows included, always suffices). A table never tracked answers as if
+ * every mark were clear; a build side of 0 rows gives 0 rows without a launch. Working memory (one
+ * byte per build row) comes from the library's allocator; one read-back (the count). */
+int qe_join_build_rows(qe_join* j, int32_t matched, qe_column* idx, int64_t* rows);
+/* Clears every mark, stream-ordered: the table can then serve another probe side. */
+int qe_join_clear_marks(qe_join* j);
 /* Semi / anti join: mask[i] = (probe row i has a match) XOR anti, so a null probe key is kept by
  * anti. `mask`: BOOL without validity, capacity >= key->length rows, whole 32-bit words written.
  * Stream-ordered, no host wait: a filter queues right behind it. */

@@ -20,8 +20,19 @@
 //   exclusive scan of the tile counts; the total is read back and checked against the capacity
 //   k_join_emit   : looks the tile's rows up again, scans their counts inside the workgroup, and
 //                   every lane writes its rows' runs
+//   with QE_JOIN_TRACK, k_join_emit<true> also sets the mark of every slot whose run it writes
 // qe_join_probe_mask
 //   k_join_mask   : one row per lane, the BOOL words built per wave with __ballot; no host wait
+// Match marks: one bit per slot of [0, slots] (the side slot included), allocated by the first call
+// that sets one.
+// qe_join_mark
+//   k_join_mark   : one row per lane, the lookup of the probe and the marking of k_join_emit<true>
+// qe_join_build_rows
+//   k_join_flag_rows : one slot per lane: a marked slot stores 1 into the bytes of its run's rows
+//                      (one working byte per build row, cleared first; a null-key row is in no run)
+//   k_join_rows_count: rows per tile of JOIN_TILE build rows whose byte equals `matched`
+//   exclusive scan of the tile counts; the total is read back and checked against the capacity
+//   k_join_rows_emit : the tile's bytes again, scanned inside the workgroup; ascending row indices
 #include "qe_rows.hpp"
 #include "qe_join_plan.hpp"
 
@@ -33,6 +44,8 @@ struct qe_join {
   int32_t* rows = nullptr; // build rows by run; NULL when every run has one row (or the table is empty)
   int64_t slots = 0, build_rows = 0, distinct = 0, max_dup = 0;
   int32_t type = 0;
+  int64_t total_rows = 0;     // the build side's rows, null keys included
+  uint32_t* marks = nullptr;  // join_mark_words(slots) words, from the first call that marks; else NULL
 };
 
 namespace qe {
@@ -65,16 +78,35 @@ __device__ __forceinline__ bool join_row_word(const JKey& K, int64_t i, uint64_t
 }
 
 // The run of key word w: its slot's meta word, 0 when the key is absent. The table is at most
-// half full, so a probe chain always ends at a free slot.
-__device__ __forceinline__ uint64_t join_lookup(const JSlot* __restrict__ tab, uint64_t S, uint64_t w) {
-  if (w == JOIN_EMPTY_WORD) return tab[S].meta;
+// half full, so a probe chain always ends at a free slot. SLOT: *slot = the slot of a hit (the side
+// slot is S); without it the parameter compiles away.
+template <bool SLOT = false>
+__device__ __forceinline__ uint64_t join_lookup(const JSlot* __restrict__ tab, uint64_t S, uint64_t w,
+                                                uint64_t* slot = nullptr) {
+  if (w == JOIN_EMPTY_WORD) {
+    if (SLOT) *slot = S;
+    return tab[S].meta;
+  }
   uint64_t s = join_home(w, S);
   for (;;) {
     const ulonglong2 e = *(const ulonglong2*)&tab[s];
-    if (e.x == w) return e.y;
+    if (e.x == w) {
+      if (SLOT) *slot = s;
+      return e.y;
+    }
     if (e.x == JOIN_EMPTY_WORD) return 0;
     s = (s + 1) & (S - 1);
   }
+}
+
+// Sets the mark of `slot`. The bit is read first and the atomic issued only when it is clear: a
+// probe with millions of rows on one key costs reads, not atomics on one address. The read is a
+// relaxed device-scope load, served by L2 where the atomics land; a plain load could keep meeting
+// a line in this CU's L1 from before the bit was set. A stale read costs one redundant atomic.
+__device__ __forceinline__ void join_set_mark(uint32_t* __restrict__ marks, uint64_t slot) {
+  uint32_t* w = marks + join_mark_word(slot);
+  const uint32_t b = join_mark_bit(slot);
+  if (!(__hip_atomic_load(w, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & b)) atomicOr(w, b);
 }
 
 __device__ __forceinline__ uint64_t wave_sum(uint64_t x) {
@@ -152,10 +184,12 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_iota(int32_t* __restrict_
 }
 
 // Pairs of probe row i: its run's meta word (0: no match or a null key) and the pairs it emits.
+// SLOT: *slot = the run's slot (set only when there is a run).
+template <bool SLOT = false>
 __device__ __forceinline__ uint64_t probe_row(const JKey& K, int64_t i, const JSlot* __restrict__ tab, uint64_t S,
-                                              bool left, int64_t* pairs) {
+                                              bool left, int64_t* pairs, uint64_t* slot = nullptr) {
   uint64_t w, m = 0;
-  if (join_row_word(K, i, &w)) m = join_lookup(tab, S, w);
+  if (join_row_word(K, i, &w)) m = join_lookup<SLOT>(tab, S, w, slot);
   const int64_t c = (int64_t)(m >> 32);
   *pairs = left && c == 0 ? 1 : c;
   return m;
@@ -184,20 +218,26 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_count(JKey K, int64_t n, 
 }
 
 // toffs[tile] = pairs of the earlier tiles; `total` = all pairs (the capacity was checked against it).
+// TRACK: every row that writes a run also marks the run's slot in `marks`, once per run; the
+// untracked instantiation takes no part of it (`marks` is then NULL and unused).
+template <bool TRACK>
 __global__ void __launch_bounds__(JOIN_THREADS) k_join_emit(JKey K, int64_t n, const JSlot* __restrict__ tab, uint64_t S,
                                                             const int32_t* __restrict__ rows, int left,
                                                             const int64_t* __restrict__ toffs, int64_t total,
-                                                            int32_t* __restrict__ probe_idx, int32_t* __restrict__ build_idx) {
+                                                            int32_t* __restrict__ probe_idx, int32_t* __restrict__ build_idx,
+                                                            uint32_t* __restrict__ marks) {
   __shared__ int64_t ws[JOIN_THREADS / 64];
   const int64_t g0 = (int64_t)blockIdx.x * JOIN_TILE;
   int64_t v[8], ex[8];
   uint64_t m[8];
+  uint64_t sl[TRACK ? 8 : 1];
 #pragma unroll
   for (int k = 0; k < 8; ++k) {
     const int64_t i = tile_elem(g0, k);
     v[k] = 0;
     m[k] = 0;
-    if (i < n) m[k] = probe_row(K, i, tab, S, left != 0, &v[k]);
+    if (TRACK) sl[TRACK ? k : 0] = 0;
+    if (i < n) m[k] = probe_row<TRACK>(K, i, tab, S, left != 0, &v[k], TRACK ? &sl[TRACK ? k : 0] : nullptr);
   }
   (void)tile_excl<int64_t, JOIN_THREADS / 64>(v, ex, ws);
   const int64_t base = toffs[blockIdx.x];
@@ -211,6 +251,8 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_emit(JKey K, int64_t n, c
     const int64_t st = (int64_t)(uint32_t)m[k];
     // a run of JOIN_COOP_MIN rows or more is written by the whole wave, 64 consecutive pairs per step
     const bool coop = JOIN_COOP_MIN > 0 && ok && rows && c >= JOIN_COOP_MIN;
+    // (before the wave's runs: a lane whose run the wave writes leaves this step right after them)
+    if (TRACK && ok && c > 0) join_set_mark(marks, sl[TRACK ? k : 0]);
     for (uint64_t big = __ballot(coop); big; big &= big - 1) {
       const int src = __builtin_ctzll(big);
       const int64_t oo = __shfl(o, src), cc = __shfl(c, src), ss = __shfl(st, src);
@@ -254,6 +296,101 @@ __global__ void __launch_bounds__(JOIN_THREADS) k_join_mask(JKey K, int64_t n, c
   }
 }
 
+// The marking of a tracked probe alone: every row with a run marks the run's slot.
+__global__ void __launch_bounds__(JOIN_THREADS) k_join_mark(JKey K, int64_t n, const JSlot* __restrict__ tab, uint64_t S,
+                                                            uint32_t* __restrict__ marks) {
+  for (int64_t i = blockIdx.x * (int64_t)JOIN_THREADS + threadIdx.x; i < n; i += (int64_t)gridDim.x * JOIN_THREADS) {
+    int64_t pairs;
+    uint64_t slot = 0;
+    if (probe_row<true>(K, i, tab, S, false, &pairs, &slot) >> 32) join_set_mark(marks, slot);
+  }
+}
+
+// flag[r] = 1 for every build row r of a marked slot's run (flag[] was cleared: a row of an unmarked
+// key, and a null-key row, which is in no run, keep 0). One slot of [0, S] per lane; a run of
+// JOIN_COOP_MIN rows or more is flagged by the whole wave, as k_join_emit writes one. Every row is
+// in at most one run, so the byte stores never meet.
+__global__ void __launch_bounds__(JOIN_THREADS) k_join_flag_rows(const JSlot* __restrict__ tab, uint64_t S,
+                                                                 const int32_t* __restrict__ rows, int64_t nn, int64_t n,
+                                                                 const uint32_t* __restrict__ marks,
+                                                                 uint8_t* __restrict__ flag) {
+  const int lane = threadIdx.x & 63;
+  const uint64_t nchunks = (S + 1 + 63) >> 6;
+  const uint64_t wave = (blockIdx.x * (uint64_t)JOIN_THREADS + threadIdx.x) >> 6;
+  const uint64_t nwaves = ((uint64_t)gridDim.x * JOIN_THREADS) >> 6;
+  for (uint64_t ch = wave; ch < nchunks; ch += nwaves) {  // the same trip count in every lane of a wave
+    const uint64_t s = ch * 64 + lane;
+    uint64_t m = 0;
+    if (s <= S && (marks[join_mark_word(s)] & join_mark_bit(s))) m = tab[s].meta;
+    const int64_t c = (int64_t)(m >> 32);
+    const int64_t st = (int64_t)(uint32_t)m;
+    if (!rows) {  // every run has one row: the slot holds it
+      if (c != 0 && st < n) flag[st] = 1;
+      continue;
+    }
+    const bool ok = c != 0 && st + c <= nn;  // (a run lies inside rows[], one entry per non-null row)
+    const bool coop = JOIN_COOP_MIN > 0 && ok && c >= JOIN_COOP_MIN;
+    for (uint64_t big = __ballot(coop); big; big &= big - 1) {
+      const int src = __builtin_ctzll(big);
+      const int64_t cc = __shfl(c, src), ss = __shfl(st, src);
+      for (int64_t j = lane; j < cc; j += 64) {
+        const int64_t r = rows[ss + j];
+        if (r >= 0 && r < n) flag[r] = 1;
+      }
+    }
+    if (!ok || coop) continue;
+    for (int64_t j = 0; j < c; ++j) {
+      const int64_t r = rows[st + j];
+      if (r >= 0 && r < n) flag[r] = 1;
+    }
+  }
+}
+
+// This thread's 8 flag bytes of the tile at g0 as 0 / 1 answers "row i < n has flag == want"; flag[]
+// is padded to whole 8-byte words.
+__device__ __forceinline__ void rows_tile(const uint8_t* __restrict__ flag, int64_t g0, int64_t n, uint32_t want,
+                                          int32_t (&v)[8]) {
+  const int64_t e0 = tile_elem(g0, 0);
+  const uint64_t f = e0 < n ? *(const uint64_t*)(flag + e0) : 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) v[k] = e0 + k < n && (uint32_t)((f >> (8 * k)) & 0xFF) == want;
+}
+
+__global__ void __launch_bounds__(JOIN_THREADS) k_join_rows_count(const uint8_t* __restrict__ flag, int64_t n, uint32_t want,
+                                                                  int64_t* __restrict__ tcount) {
+  __shared__ int64_t ws[JOIN_THREADS / 64];
+  int32_t v[8];
+  rows_tile(flag, (int64_t)blockIdx.x * JOIN_TILE, n, want, v);
+  uint64_t t = 0;
+#pragma unroll
+  for (int k = 0; k < 8; ++k) t += (uint64_t)v[k];
+  t = wave_sum(t);
+  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = (int64_t)t;
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int64_t all = 0;
+    for (int w = 0; w < JOIN_THREADS / 64; ++w) all += ws[w];
+    tcount[blockIdx.x] = all;
+  }
+}
+
+// toffs[tile] = rows of the earlier tiles; `total` = all rows (the capacity was checked against it).
+__global__ void __launch_bounds__(JOIN_THREADS) k_join_rows_emit(const uint8_t* __restrict__ flag, int64_t n, uint32_t want,
+                                                                 const int64_t* __restrict__ toffs, int64_t total,
+                                                                 int32_t* __restrict__ idx) {
+  __shared__ int32_t ws[JOIN_THREADS / 64];
+  const int64_t g0 = (int64_t)blockIdx.x * JOIN_TILE;
+  int32_t v[8], ex[8];
+  rows_tile(flag, g0, n, want, v);
+  (void)tile_excl<int32_t, JOIN_THREADS / 64>(v, ex, ws);
+  const int64_t base = toffs[blockIdx.x];
+#pragma unroll
+  for (int k = 0; k < 8; ++k) {
+    const int64_t o = base + ex[k];
+    if (v[k] && o >= 0 && o < total) idx[o] = (int32_t)tile_elem(g0, k);  // (the second pass counts what the first did)
+  }
+}
+
 namespace {
 
 int check_key(const char* what, const qe_column* key) {
@@ -273,6 +410,19 @@ int check_probe(const char* what, const qe_join* j, const qe_column* key) {
   QE_CHECK(join_compatible(j->type, key->type), QE_ERR_INVALID_ARG,
            "%s: a probe key of type %d does not join a build key of type %d (FLOAT64 joins only FLOAT64)", what, key->type,
            j->type);
+  return QE_OK;
+}
+
+// The mark bitmap, allocated and cleared (stream-ordered) by the first call that marks.
+int ensure_marks(qe_join* j) {
+  if (j->marks) return QE_OK;
+  const size_t bytes = (size_t)join_mark_words(j->slots) * 4;
+  Blocks blk(j->ctx);
+  void* p;
+  QE_TRY(blk.alloc(bytes, &p));
+  QE_HIP(hipMemsetAsync(p, 0, bytes, j->ctx->stream));
+  blk.keep(p);
+  j->marks = (uint32_t*)p;
   return QE_OK;
 }
 
@@ -360,6 +510,7 @@ int qe_join_build(qe_ctx* ctx, const qe_column* key, qe_join** out) {
   j->rows = rows;
   j->slots = S;
   j->build_rows = nn;
+  j->total_rows = n;
   j->distinct = distinct;
   j->max_dup = max_dup;
   j->type = key->type;
@@ -374,6 +525,7 @@ int qe_join_destroy(qe_join* j) {
   if (j->ctx) {
     dev_free(j->ctx, j->tab);
     dev_free(j->ctx, j->rows);
+    dev_free(j->ctx, j->marks);
   }
   delete j;
   return QE_OK;
@@ -394,7 +546,10 @@ int qe_join_probe(qe_join* j, const qe_column* key, int32_t kind, qe_column* pro
                   int64_t* pairs) {
   QE_TRY(check_probe("join probe", j, key));
   qe_ctx* ctx = j->ctx;
-  QE_CHECK(kind == QE_JOIN_INNER || kind == QE_JOIN_LEFT, QE_ERR_INVALID_ARG, "join probe: kind %d", kind);
+  int32_t base;
+  bool track;
+  QE_CHECK(join_probe_kind(kind, &base, &track), QE_ERR_INVALID_ARG, "join probe: kind %d", kind);
+  const int left = base == QE_JOIN_LEFT ? 1 : 0;
   QE_CHECK(probe_idx && build_idx && pairs, QE_ERR_INVALID_ARG, "join probe: null output");
   QE_CHECK(probe_idx->type == QE_TYPE_INT32 && !probe_idx->validity && build_idx->type == QE_TYPE_INT32 && !build_idx->validity,
            QE_ERR_INVALID_ARG, "join probe: the index columns must be INT32 without validity");
@@ -413,7 +568,7 @@ int qe_join_probe(qe_join* j, const qe_column* key, int32_t kind, qe_column* pro
   QE_TRY(blk.alloc((size_t)ntiles * 8, (void**)&tcount));
   QE_TRY(blk.alloc((size_t)(ntiles + 1) * 8, (void**)&toffs));
   hipLaunchKernelGGL(k_join_count, dim3((unsigned)ntiles), dim3(JOIN_THREADS), 0, ctx->stream, K, n, (const JSlot*)j->tab,
-                     (uint64_t)j->slots, kind == QE_JOIN_LEFT ? 1 : 0, tcount);
+                     (uint64_t)j->slots, left, tcount);
   QE_TRY(launch_check("k_join_count"));
   QE_TRY(exclusive_scan_i64(ctx, tcount, toffs, ntiles));
   void* hp;
@@ -426,10 +581,13 @@ int qe_join_probe(qe_join* j, const qe_column* key, int32_t kind, qe_column* pro
   QE_CHECK(total <= cap, QE_ERR_CAPACITY, "join probe: the index columns hold %lld rows, need %lld", (long long)cap,
            (long long)total);
   QE_CHECK(total == 0 || (probe_idx->values && build_idx->values), QE_ERR_INVALID_ARG, "join probe: an index column has no values");
-  if (total > 0) {
-    hipLaunchKernelGGL(k_join_emit, dim3((unsigned)ntiles), dim3(JOIN_THREADS), 0, ctx->stream, K, n, (const JSlot*)j->tab,
-                       (uint64_t)j->slots, (const int32_t*)j->rows, kind == QE_JOIN_LEFT ? 1 : 0, (const int64_t*)toffs, total,
-                       (int32_t*)probe_idx->values, (int32_t*)build_idx->values);
+  if (total > 0) {  // (no pair, no match: nothing to mark either)
+    // marking is the emit pass's: a call refused above has left the marks alone
+    if (track) QE_TRY(ensure_marks(j));
+    hipLaunchKernelGGL(track ? k_join_emit<true> : k_join_emit<false>, dim3((unsigned)ntiles), dim3(JOIN_THREADS), 0,
+                       ctx->stream, K, n, (const JSlot*)j->tab, (uint64_t)j->slots, (const int32_t*)j->rows, left,
+                       (const int64_t*)toffs, total, (int32_t*)probe_idx->values, (int32_t*)build_idx->values,
+                       track ? j->marks : (uint32_t*)nullptr);
     QE_TRY(launch_check("k_join_emit"));
   }
   probe_idx->length = build_idx->length = total;
@@ -452,6 +610,78 @@ int qe_join_probe_mask(qe_join* j, const qe_column* key, int32_t anti, qe_column
   hipLaunchKernelGGL(k_join_mask, dim3(stride_grid(ctx, n)), dim3(JOIN_THREADS), 0, ctx->stream, K, n, (const JSlot*)j->tab,
                      (uint64_t)j->slots, anti ? 1 : 0, (uint32_t*)mask->values);
   return launch_check("k_join_mask");
+}
+
+int qe_join_mark(qe_join* j, const qe_column* key) {
+  QE_TRY(check_probe("join mark", j, key));
+  qe_ctx* ctx = j->ctx;
+  const int64_t n = key->length;
+  if (n == 0) return QE_OK;
+  QE_TRY(ensure_marks(j));
+  const JKey K{key->values, key->validity, key->type};
+  hipLaunchKernelGGL(k_join_mark, dim3(stride_grid(ctx, n)), dim3(JOIN_THREADS), 0, ctx->stream, K, n, (const JSlot*)j->tab,
+                     (uint64_t)j->slots, j->marks);
+  return launch_check("k_join_mark");
+}
+
+int qe_join_clear_marks(qe_join* j) {
+  QE_CHECK(j != nullptr && j->ctx != nullptr, QE_ERR_INVALID_ARG, "join clear marks: null join");
+  QE_TRY(ctx_enter(j->ctx));
+  if (j->marks) QE_HIP(hipMemsetAsync(j->marks, 0, (size_t)join_mark_words(j->slots) * 4, j->ctx->stream));
+  return QE_OK;
+}
+
+int qe_join_build_rows(qe_join* j, int32_t matched, qe_column* idx, int64_t* rows) {
+  QE_CHECK(j != nullptr && j->ctx != nullptr, QE_ERR_INVALID_ARG, "join build rows: null join");
+  qe_ctx* ctx = j->ctx;
+  QE_TRY(ctx_enter(ctx));
+  QE_CHECK(idx && rows, QE_ERR_INVALID_ARG, "join build rows: null output");
+  QE_CHECK(idx->type == QE_TYPE_INT32 && !idx->validity, QE_ERR_INVALID_ARG,
+           "join build rows: the index column must be INT32 without validity");
+  const int64_t cap = idx->length;
+  QE_CHECK(cap >= 0, QE_ERR_INVALID_ARG, "join build rows: negative capacity");
+  const int64_t n = j->total_rows;
+  *rows = 0;
+  if (n == 0) {
+    idx->length = 0;
+    return QE_OK;
+  }
+  const int64_t ntiles = (int64_t)div_up((uint64_t)n, JOIN_TILE);
+  const size_t fbytes = ((size_t)n + 7) & ~(size_t)7;  // k_join_rows_* read whole 8-byte words
+  Blocks blk(ctx);
+  uint8_t* flag;
+  int64_t *tcount, *toffs;
+  QE_TRY(blk.alloc(fbytes, (void**)&flag));
+  QE_TRY(blk.alloc((size_t)ntiles * 8, (void**)&tcount));
+  QE_TRY(blk.alloc((size_t)(ntiles + 1) * 8, (void**)&toffs));
+  QE_HIP(hipMemsetAsync(flag, 0, fbytes, ctx->stream));
+  if (j->marks && j->build_rows > 0) {  // (never tracked: every mark is clear, every row unmatched)
+    hipLaunchKernelGGL(k_join_flag_rows, dim3(stride_grid(ctx, j->slots + 1)), dim3(JOIN_THREADS), 0, ctx->stream,
+                       (const JSlot*)j->tab, (uint64_t)j->slots, (const int32_t*)j->rows, j->build_rows, n,
+                       (const uint32_t*)j->marks, flag);
+    QE_TRY(launch_check("k_join_flag_rows"));
+  }
+  const uint32_t want = matched ? 1u : 0u;
+  hipLaunchKernelGGL(k_join_rows_count, dim3((unsigned)ntiles), dim3(JOIN_THREADS), 0, ctx->stream, (const uint8_t*)flag, n,
+                     want, tcount);
+  QE_TRY(launch_check("k_join_rows_count"));
+  QE_TRY(exclusive_scan_i64(ctx, tcount, toffs, ntiles));
+  void* hp;
+  QE_TRY(ctx_pinned(ctx, 8, &hp));
+  QE_HIP(hipMemcpyAsync(hp, toffs + ntiles, 8, hipMemcpyDeviceToHost, ctx->stream));
+  QE_TRY(ctx_sync(ctx));
+  const int64_t total = *(const int64_t*)hp;
+  *rows = total;
+  QE_CHECK(total <= cap, QE_ERR_CAPACITY, "join build rows: the index column holds %lld rows, need %lld", (long long)cap,
+           (long long)total);
+  QE_CHECK(total == 0 || idx->values, QE_ERR_INVALID_ARG, "join build rows: the index column has no values");
+  if (total > 0) {
+    hipLaunchKernelGGL(k_join_rows_emit, dim3((unsigned)ntiles), dim3(JOIN_THREADS), 0, ctx->stream, (const uint8_t*)flag, n,
+                       want, (const int64_t*)toffs, total, (int32_t*)idx->values);
+    QE_TRY(launch_check("k_join_rows_emit"));
+  }
+  idx->length = total;
+  return QE_OK;
 }
 
 }  // extern "C"

@@ -14,6 +14,8 @@
 // build rows); home slot = fmix64(key word) & (slots - 1). Every 64-bit value is a legal key word:
 // the word JOIN_EMPTY_WORD marks a free slot in the key array and, as a key, lives in the side slot
 // `slots` (one past the probed range), as EMPTY_KEY does in the GROUP BY tables.
+// Match marks (RIGHT / FULL OUTER and the build-side semi / anti joins): one bit per slot, the side
+// slot included; the probe kinds that set them are decoded here (tests/native/join_marks_host.cpp).
 #pragma once
 
 #include <stdint.h>
@@ -83,5 +85,18 @@ QE_JOIN_HD int64_t join_slots(int64_t rows) {
 }
 
 QE_JOIN_HD uint64_t join_home(uint64_t word, uint64_t slots) { return (uint64_t)fmix64(word) & (slots - 1); }
+
+// qe_join_probe's `kind`: QE_JOIN_INNER or QE_JOIN_LEFT, alone or with the QE_JOIN_TRACK bit (the
+// probe then marks the build keys it matches). false: any other value, refused.
+QE_JOIN_HD bool join_probe_kind(int32_t kind, int32_t* base, bool* track) {
+  *base = kind & ~(int32_t)QE_JOIN_TRACK;
+  *track = (kind & QE_JOIN_TRACK) != 0;
+  return *base == QE_JOIN_INNER || *base == QE_JOIN_LEFT;
+}
+
+// Match marks: one bit per slot of [0, slots], the side slot `slots` included, in 32-bit words.
+QE_JOIN_HD int64_t join_mark_words(int64_t slots) { return (slots + 1 + 31) >> 5; }
+QE_JOIN_HD uint64_t join_mark_word(uint64_t slot) { return slot >> 5; }
+QE_JOIN_HD uint32_t join_mark_bit(uint64_t slot) { return 1u << (slot & 31); }
 
 }  // namespace qe

@@ -49,6 +49,7 @@ AGG_SUM, AGG_MIN, AGG_MAX, AGG_COUNT, AGG_COUNT_STAR, AGG_AVG = 1, 2, 3, 4, 5, 6
 SORT_DESC, SORT_NULLS_FIRST = 1, 2  # qe_sort_indices flag bits (0: ascending, nulls last)
 TOPK_AUTO, TOPK_SELECT, TOPK_SORT = 0, 1, 2  # qe_topk_indices modes
 JOIN_INNER, JOIN_LEFT = 0, 1  # qe_join_probe kinds
+JOIN_TRACK = 0x100  # OR-ed into a kind: the probe also marks the build keys it matches
 # qe_window_eval functions and frames (every frame starts at the partition's first row)
 (WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT_STAR, WIN_COUNT, WIN_SUM, WIN_MIN, WIN_MAX, WIN_LAG,
  WIN_LEAD) = range(1, 11)
@@ -262,6 +263,9 @@ SIGNATURES = [
     ("qe_join_probe", C.c_int, [_P, _COLP, C.c_int32, _COLP, _COLP, _I64P]),
     ("qe_join_probe_mask", C.c_int, [_P, _COLP, C.c_int32, _COLP]),
     ("qe_join_stats", C.c_int, [_P, _I64P, _I64P, _I64P, _I64P]),
+    ("qe_join_mark", C.c_int, [_P, _COLP]),
+    ("qe_join_build_rows", C.c_int, [_P, C.c_int32, _COLP, _I64P]),
+    ("qe_join_clear_marks", C.c_int, [_P]),
     ("qe_take_or_null", C.c_int, [_P, _COLP, _COLP, C.c_int32, _COLP, _I64P]),
     ("qe_agg_global", C.c_int, [_P, _COLP, _COLP, C.POINTER(QeGlobalAgg)]),
     ("qe_agg_global_partial", C.c_int, [_P, _COLP, _COLP, C.c_int64, _P]),

@@ -434,9 +434,10 @@ class WindowExec(PhysicalPlan):
 class JoinTable:
     """The device hash table of one build side (qe_join_build); close() releases it."""
 
-    def __init__(self, ctx, handle):
+    def __init__(self, ctx, handle, rows: int = 0):
         self.ctx = ctx
         self.handle = handle
+        self.rows = rows  # the build side's rows, null keys included
 
     def close(self) -> None:
         if getattr(self, "handle", None) is not None:
@@ -456,7 +457,7 @@ def join_build(key: DeviceColumn) -> JoinTable:
     h = N.C.c_void_p()
     kc = key.as_c()
     N.check(N.lib().qe_join_build(key.ctx.handle, N.C.byref(kc), N.C.byref(h)))
-    return JoinTable(key.ctx, h)
+    return JoinTable(key.ctx, h, key.length)
 
 
 def join_stats(table: JoinTable):
@@ -468,7 +469,8 @@ def join_stats(table: JoinTable):
 
 def join_probe(table: JoinTable, key: DeviceColumn, kind: int = N.JOIN_INNER, capacity: Optional[int] = None):
     """qe_join_probe: the (probe row, build row) INT32 index columns of one probe batch, ordered by
-    probe row, then build row; N.JOIN_LEFT pairs an unmatched row with -1. The first try sizes the
+    probe row, then build row; N.JOIN_LEFT pairs an unmatched row with -1. `kind | N.JOIN_TRACK`: the
+    same pairs, and the build keys the batch matched are marked (join_build_rows). The first try sizes the
     outputs at `capacity` rows (default: the batch's rows, which a build side of unique keys never
     exceeds); a short one is carved again at the exact count the call reported: two tries at most."""
     ctx = key.ctx
@@ -496,6 +498,30 @@ def join_probe_mask(table: JoinTable, key: DeviceColumn, anti: bool = False) -> 
     kc, mc = key.as_c(), mask.as_c()
     N.check(N.lib().qe_join_probe_mask(table.handle, N.C.byref(kc), 1 if anti else 0, N.C.byref(mc)))
     return mask
+
+
+def join_mark(table: JoinTable, key: DeviceColumn) -> None:
+    """qe_join_mark: marks the build keys that `key`'s non-null rows equal, as a tracked probe does,
+    and writes nothing else. Stream-ordered."""
+    kc = key.as_c()
+    N.check(N.lib().qe_join_mark(table.handle, N.C.byref(kc)))
+
+
+def join_build_rows(table: JoinTable, matched: bool) -> DeviceColumn:
+    """qe_join_build_rows: the ascending INT32 indices of the build rows whose key is marked
+    (matched) or is not (unmatched: the null-key rows are among these). Sized at the build side's
+    rows, so one call always suffices."""
+    idx = DeviceColumn.empty(N.TYPE_INT32, table.rows, False, ctx=table.ctx)
+    ic = idx.as_c()
+    rows = N.C.c_int64()
+    N.check(N.lib().qe_join_build_rows(table.handle, 1 if matched else 0, N.C.byref(ic), N.C.byref(rows)))
+    idx.length = rows.value
+    return idx
+
+
+def join_clear_marks(table: JoinTable) -> None:
+    """qe_join_clear_marks: every mark clear again (the table can serve another left input)."""
+    N.check(N.lib().qe_join_clear_marks(table.handle))
 
 
 def _taken_bytes(indices: DeviceColumn, cols: Sequence[DeviceColumn]) -> List[Optional[int]]:
@@ -576,24 +602,60 @@ class _JoinKeyEncoder:
             d.close()
 
 
+def _null_columns(ctx, schema: Schema, n: int) -> List[DeviceColumn]:
+    """n all-null rows of every field of `schema`: zero values, clear validity; a UTF8 column has
+    n + 1 zero offsets and no bytes."""
+    import torch
+
+    from .columnar import bitmap_bytes
+
+    dev = ctx.torch_device
+    cols = []
+    for f in schema.fields:
+        if f.dataType == N.TYPE_UTF8:
+            cols.append(DeviceColumn(N.TYPE_UTF8, n, torch.zeros(1, dtype=torch.uint8, device=dev),
+                                     torch.zeros(max(bitmap_bytes(n), 4), dtype=torch.uint8, device=dev),
+                                     torch.zeros(n + 1, dtype=torch.int32, device=dev), ctx))
+            cols[-1].max_len = 0
+        else:
+            c = DeviceColumn.empty(f.dataType, n, True, ctx=ctx)
+            c.values.zero_()
+            cols.append(c)
+    return cols
+
+
 class HashJoinExec(PhysicalPlan):
     """Equi-join (build-defined; the reference's SQL has no JOIN). `on`: 1..MAX_KEYS pairs
-    (left Expression, right Expression); kind: inner, left, semi or anti. The RIGHT child is the build
-    side: drained once into one batch (concat_batches) and hashed (qe_join_build). The LEFT child
-    streams: one output batch per input batch, rows in probe order and, within a probe row, in build
-    row order. A null key matches nothing.
-    Schema: inner / left: the left fields then the right fields (all null for an unmatched row of
-    left); semi / anti: the left fields. An empty build side gives 0-row batches (inner, semi),
-    all-null right columns (left) or every row (anti)."""
+    (left Expression, right Expression); kind: one of KINDS (inner, left, semi, anti) or of
+    BUILD_SIDE_KINDS (right, full_outer, right_semi, right_anti). The RIGHT child is the build side of
+    every kind: drained once into one batch (concat_batches) and hashed (qe_join_build). The LEFT child
+    streams. A null key matches nothing.
+    KINDS give one output batch per left batch, rows in probe order and, within a probe row, in build
+    row order. Schema: inner / left: the left fields then the right fields (all null for an
+    unmatched row of left); semi / anti: the left fields. An empty build side gives 0-row batches
+    (inner, semi), all-null right columns (left) or every row (anti).
+    BUILD_SIDE_KINDS need to know which build rows ever found a partner (the table's match marks), so
+    they end with ONE more batch after the last left batch, yielded even when it has 0 rows: L left
+    batches give L + 1 output batches (right, full_outer) or 1 (right_semi, right_anti).
+      right       per left batch the inner pairs, then the unmatched build rows in build-row order with
+                  every left column null. Schema: the left fields then the right fields.
+      full_outer  the same with the left kind's pairs per batch ("full" is not a name of it).
+      right_semi  nothing per left batch; at the end the matched build rows in build-row order.
+      right_anti  likewise the unmatched build rows (a null-key build row is unmatched).
+                  Schema of both: the right fields.
+    A left child that yields no batch gives the final batch alone: every build row for right,
+    full_outer and right_anti, none for right_semi. An empty build side gives a final batch of 0 rows."""
 
     KINDS = ("inner", "left", "semi", "anti")
+    BUILD_SIDE_KINDS = ("right", "full_outer", "right_semi", "right_anti")
 
     def __init__(self, left: PhysicalPlan, right: PhysicalPlan, on, kind: str = "inner"):
         on = list(on)
         if not 1 <= len(on) <= N.MAX_KEYS:
             raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG, f"a join takes 1..{N.MAX_KEYS} key pairs")
-        if kind not in self.KINDS:
-            raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG, f"join kind {kind!r} (one of {self.KINDS})")
+        if kind not in self.KINDS + self.BUILD_SIDE_KINDS:
+            raise N.IllegalArgumentException(N.QE_ERR_INVALID_ARG,
+                                             f"join kind {kind!r} (one of {self.KINDS + self.BUILD_SIDE_KINDS})")
         self.left = left
         self.right = right
         self.on = [(le, re) for le, re in on]
@@ -602,6 +664,8 @@ class HashJoinExec(PhysicalPlan):
     def schema(self) -> Schema:
         if self.kind in ("semi", "anti"):
             return self.left.schema()
+        if self.kind in ("right_semi", "right_anti"):
+            return self.right.schema()
         return Schema(list(self.left.schema().fields) + list(self.right.schema().fields))
 
     def children(self) -> List[PhysicalPlan]:
@@ -642,11 +706,22 @@ class HashJoinExec(PhysicalPlan):
                 if self.kind in ("semi", "anti"):
                     yield filter_batch(batch, join_probe_mask(table, key, anti=self.kind == "anti"))
                     continue
-                left = self.kind == "left"
-                pi, bi = join_probe(table, key, N.JOIN_LEFT if left else N.JOIN_INNER)
+                if self.kind in ("right_semi", "right_anti"):
+                    join_mark(table, key)
+                    continue
+                left = self.kind in ("left", "full_outer")
+                track = N.JOIN_TRACK if self.kind in ("right", "full_outer") else 0
+                pi, bi = join_probe(table, key, (N.JOIN_LEFT if left else N.JOIN_INNER) | track)
                 lcols = take(pi, batch.fields, _taken_bytes(pi, batch.fields))
                 rcols = (take_or_null if left else take)(bi, build.fields, _taken_bytes(bi, build.fields))
                 yield RecordBatch(schema, lcols + rcols)
+            if self.kind in self.BUILD_SIDE_KINDS:  # the one batch only the whole left input can settle
+                rows = join_build_rows(table, matched=self.kind == "right_semi")
+                rcols = take(rows, build.fields)  # (no index repeats: the input's bytes bound the output's)
+                if self.kind in ("right_semi", "right_anti"):
+                    yield RecordBatch(schema, rcols)
+                else:
+                    yield RecordBatch(schema, _null_columns(table.ctx, self.left.schema(), rows.length) + rcols)
         finally:
             if table is not None:
                 table.close()

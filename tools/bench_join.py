@@ -22,6 +22,16 @@ probe = 2 x probe rows x 8 (the count and the emit pass each read the keys) + pa
 written) + pairs x 4 (rows[] read) when the build side has duplicate keys. The table gathers are
 listed apart (gather_bytes = 2 x probe rows x one 64-byte line): they are served by the caches for a
 table that fits them and by HBM otherwise. TB/s = the pass's bytes over its median time.
+
+--marks adds, per case and inside the same loop (so on the same table, right after the untracked
+probe): the tracked probe (QE_JOIN_INNER | QE_JOIN_TRACK, the same capacity; the table is fresh in
+every repetition, so the time includes allocating and clearing the mark bitmap) and, after it,
+join_build_rows(matched). New keys: qe_probe_tracked_ms (+ _min / _max), tracked_ratio = tracked ms /
+untracked ms, matched_rows, build_rows_ms (+ _min / _max), build_rows_bytes and build_rows_gb_per_s.
+build_rows_bytes is the least the call can move: the bitmap (slots / 8) and the slots (slots x 16)
+read, rows[] read (build rows x 4) when the build side has duplicate keys, the matched indices written
+(matched rows x 4); its working bytes (one per build row, written once and read twice) are on top.
+The call reads its count back, so its time holds that round trip too.
 """
 import argparse
 import json
@@ -42,13 +52,14 @@ def main() -> int:
     ap.add_argument("--warmup", type=int, default=2)
     ap.add_argument("--scale", type=float, default=1.0)
     ap.add_argument("--out", default=str(ROOT / "profiles" / "join.json"))
+    ap.add_argument("--marks", action="store_true", help="also time the tracked probe and join_build_rows")
     args = ap.parse_args()
 
     import torch
 
     from kquery import native as N
     from kquery.columnar import Context, DeviceColumn
-    from kquery.operators import join_build, join_probe, join_stats
+    from kquery.operators import join_build, join_build_rows, join_probe, join_stats
 
     if not torch.cuda.is_available():
         print("bench_join needs a GPU (there is no CPU fallback)", file=sys.stderr)
@@ -121,11 +132,21 @@ def main() -> int:
             row["torch"] = f"not measured: {str(e).splitlines()[0][:120]}"
             with_torch = False
         del pi, bi
-        qb, qp, tb, tp = [], [], [], []
+        qb, qp, tb, tp, qt, qr = [], [], [], [], [], []
+        matched_rows = 0
         for r in range(args.warmup + args.reps):
             ms_b, table = timed(lambda: join_build(bc))
             ms_p, out = timed(lambda: join_probe(table, pc, N.JOIN_INNER, capacity=pairs))
             del out
+            if args.marks:
+                ms_t, out = timed(lambda: join_probe(table, pc, N.JOIN_INNER | N.JOIN_TRACK, capacity=pairs))
+                del out
+                ms_r, out = timed(lambda: join_build_rows(table, True))
+                matched_rows = out.length
+                del out
+                if r >= args.warmup:
+                    qt.append(ms_t)
+                    qr.append(ms_r)
             table.close()
             if with_torch:
                 ms_tb, (sk, perm) = timed(lambda: torch_build(b))
@@ -146,6 +167,14 @@ def main() -> int:
                     "build_tb_per_s": round(build_bytes / (mb * 1e-3) / 1e12, 4),
                     "probe_tb_per_s": round(probe_bytes / (mp * 1e-3) / 1e12, 4),
                     "probe_rows_per_us": round(p.numel() / (mp * 1e3), 2), "pairs_per_us": round(pairs / (mp * 1e3), 2)})
+        if args.marks:
+            mt, mr = statistics.median(qt), statistics.median(qr)
+            rows_bytes = slots // 8 + slots * 16 + (b.numel() * 4 if max_dup > 1 else 0) + matched_rows * 4
+            row.update({"qe_probe_tracked_ms": round(mt, 4), "qe_probe_tracked_ms_min": round(min(qt), 4),
+                        "qe_probe_tracked_ms_max": round(max(qt), 4), "tracked_ratio": round(mt / mp, 4),
+                        "matched_rows": matched_rows, "build_rows_ms": round(mr, 4), "build_rows_ms_min": round(min(qr), 4),
+                        "build_rows_ms_max": round(max(qr), 4), "build_rows_bytes": rows_bytes,
+                        "build_rows_gb_per_s": round(rows_bytes / (mr * 1e-3) / 1e9, 3)})
         if with_torch:
             mtb, mtp = statistics.median(tb), statistics.median(tp)
             row.update({"torch_build_ms": round(mtb, 4), "torch_probe_ms": round(mtp, 4),
