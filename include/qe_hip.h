@@ -326,10 +326,14 @@ int qe_topk_last_stats(qe_ctx* ctx, int64_t stats[4]);
 #define QE_WIN_MAX 8         /* (MaxAccumulator's fold over the frame in window order, below) */
 #define QE_WIN_LAG 9         /* x of the row `offset` positions earlier in the partition, nulls included */
 #define QE_WIN_LEAD 10       /* ... later; null where that position lies outside the partition */
-/* Every frame starts at the partition's first row and ends at: */
+#define QE_WIN_FIRST_VALUE 11 /* x of the frame's first row, nulls included; null when the frame is empty */
+#define QE_WIN_LAST_VALUE 12  /* ... of its last row (both: qe_window_eval_frames only) */
+/* These three frames start at the partition's first row and end at: */
 #define QE_FRAME_ROWS 0      /* the current row */
 #define QE_FRAME_RANGE 1     /* the last row of the current row's peer group */
 #define QE_FRAME_PARTITION 2 /* the partition's last row */
+/* ROWS BETWEEN lo AND hi, counted in rows from the current row: */
+#define QE_FRAME_ROWS_BETWEEN 3 /* reads bounds[k]; qe_window_eval_frames only */
 typedef struct qe_window_fn {
   int32_t fn;     /* QE_WIN_* */
   int32_t frame;  /* QE_FRAME_*; must be one of them for every function, read by COUNT* / SUM / MIN / MAX */
@@ -337,6 +341,12 @@ typedef struct qe_window_fn {
   int32_t reserved;
   int64_t offset; /* LAG / LEAD: any int64 >= 0 (0 gives x itself); ignored otherwise */
 } qe_window_fn;
+/* The ends of a QE_FRAME_ROWS_BETWEEN frame as row offsets from the current row: negative is
+ * PRECEDING, 0 the current row, positive FOLLOWING. INT64_MIN is UNBOUNDED PRECEDING and INT64_MAX
+ * UNBOUNDED FOLLOWING, by the arithmetic below and not as special values. */
+typedef struct qe_window_bounds {
+  int64_t lo, hi;
+} qe_window_bounds;
 
 /* Run boundaries along a permutation. `order`: INT32 without validity, n rows; keys: 0..QE_MAX_KEYS
  * columns of n rows, any type a sort key may have (UTF8 compared by bytes at any length). `starts`:
@@ -358,7 +368,8 @@ int qe_window_boundaries(qe_ctx* ctx, const qe_column* keys, int32_t nkeys, cons
  * is NaN, otherwise the extreme of the non-NaN values; of values that compare equal (-0.0, +0.0) the
  * earliest in window order.
  * QE_ERR_UNSUPPORTED: SUM of FLOAT64 / DATE32 / UINT8 / BOOL / UTF8, MIN / MAX / LAG / LEAD of BOOL /
- * UTF8. QE_ERR_INVALID_ARG: an unknown function or frame, an offset < 0, an input index outside
+ * UTF8. QE_ERR_INVALID_ARG: an unknown function or frame (QE_WIN_FIRST_VALUE, QE_WIN_LAST_VALUE and
+ * QE_FRAME_ROWS_BETWEEN are unknown to this call), an offset < 0, an input index outside
  * [0, ninputs), `order` not INT32 or not of n rows, an input or boundary column of another length, an
  * output of the wrong type or without the validity buffer it needs. A refused call writes nothing.
  * An entry of `order` outside [0, n) reads and writes nothing out of range and fails the call with
@@ -369,6 +380,29 @@ int qe_window_boundaries(qe_ctx* ctx, const qe_column* keys, int32_t nkeys, cons
 int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_starts,
                    const qe_column* peer_starts, const qe_column* inputs, int32_t ninputs,
                    const qe_window_fn* fns, int32_t nfns, qe_column* outs);
+/* qe_window_eval with two more functions and one more frame; everything qe_window_eval promises
+ * holds here (outputs at the input's row positions, the validity rules, a null result's value is 0, a
+ * refused call writes nothing, a bad `order` entry fails the call, stream order with the flag read as
+ * the one host wait, one launch of one workgroup for n <= small_max, results bit-identical from run
+ * to run), and a call without the new ids computes what qe_window_eval computes.
+ * For position i of a partition that occupies positions [P, Pe]:
+ *   QE_FRAME_ROWS / RANGE / PARTITION mean what they mean above; `bounds` is not read for them and
+ *   may be NULL when no function has frame QE_FRAME_ROWS_BETWEEN.
+ *   QE_FRAME_ROWS_BETWEEN with bounds[k] = {lo, hi}: the frame is [s, e] = [max(P, i + lo),
+ *   min(Pe, i + hi)] in exact integer arithmetic, empty when s > e. Every int64 pair is legal, lo > hi
+ *   included (every frame is then empty); the bounds are compared against P - i and Pe - i and never
+ *   added to i before that. With bounds == NULL the frame is QE_ERR_INVALID_ARG, for any function.
+ * COUNT(*) = max(0, e - s + 1); COUNT(x) the non-null rows of [s, e]; SUM (INT64 / INT32 only) wraps,
+ * skips nulls and is null when the frame holds no value. MIN / MAX: Min / MaxAccumulator's fold,
+ * started fresh, over the frame's rows in window order: the FLOAT64 rule above applied to [s, e], null
+ * when the frame holds no value. FIRST_VALUE / LAST_VALUE: x of row s / row e, nulls included, null
+ * when the frame is empty; the types LAG takes, the input's type out, a validity buffer required;
+ * under the three older frames s = P. The ranks and LAG / LEAD ignore the frame (any known id).
+ * MIN / MAX cost the same per row and the same working memory whatever hi - lo is. */
+int qe_window_eval_frames(qe_ctx* ctx, const qe_column* order, const qe_column* part_starts,
+                          const qe_column* peer_starts, const qe_column* inputs, int32_t ninputs,
+                          const qe_window_fn* fns, const qe_window_bounds* bounds, int32_t nfns,
+                          qe_column* outs);
 /* Measurement hook: positions per tile of the multi-workgroup scans (a tile of the scans over the
  * boundary bitmaps' words covers 32 x tile_rows rows), and the largest n the one-workgroup path takes. */
 int qe_window_layout(int32_t* tile_rows, int32_t* small_max);

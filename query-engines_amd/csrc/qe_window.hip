@@ -1,4 +1,5 @@
-// Window functions: qe_window_boundaries, qe_window_eval, qe_window_layout.
+// Window functions: qe_window_boundaries, qe_window_eval, qe_window_eval_frames,
+// qe_window_layout.
 //
 // Everything works on SORTED POSITIONS i = 0 .. n-1 of the permutation `order` (row order[i] stands
 // at position i) until the last step, which runs one lane per INPUT ROW through the inverse
@@ -15,7 +16,11 @@
 //                a gathered input (SUM and COUNT(x) of a frame [P, e] are S[e] - S[P-1], exact modulo
 //                2^64, so this scan is not segmented), and the segmented MIN / MAX scan whose element
 //                carries (best non-NaN value, has a value, the first value is NaN, has a non-NaN
-//                value) and keeps the left operand on ties.
+//                value) and keeps the window-earlier operand on ties. MIN / MAX over a bounded frame
+//                (ROWS BETWEEN lo AND hi, at most L = hi - lo + 1 rows) reads two such scans that also
+//                restart at every block of L positions, one from the left and one from the right: a
+//                frame straddles at most one block edge, so it is the backward scan at its first
+//                position combined with the forward scan at its last, whatever L is.
 //                A tile is WIN_THREADS x WIN_ITEMS consecutive elements; carries cross tiles by tile
 //                reduce -> one workgroup scanning the tile aggregates -> apply (no look-back, nothing
 //                spins).
@@ -46,13 +51,15 @@ static_assert(sizeof(WinElem) == WIN_ELEM_BYTES, "window_tile_bytes sizes the ti
 
 enum { WS_PREV = 0, WS_NEXT, WS_POPC, WS_SUM, WS_MIN, WS_MAX };  // what a scan job scans
 constexpr int32_t WF_HAS = 1, WF_SEEDNAN = 2, WF_HASNUM = 4, WF_RESET = 8;
-constexpr int WIN_MAX_JOBS = WIN_WORD_SCANS + QE_MAX_AGGS;
+constexpr int WIN_MAX_JOBS = WIN_WORD_SCANS + 2 * QE_MAX_AGGS;  // a bounded MIN / MAX reads two position scans
 constexpr int WIN_WAVES = WIN_THREADS / 64;
 constexpr int64_t WIN_CANON_NAN = 0x7FF8000000000000ll;
 
 struct WinJob {
   int32_t src;      // WS_*
   int32_t in_type;  // position scans: the input column's type
+  int32_t back;     // MIN / MAX scans: element k is position count - 1 - k (the scan runs from the right)
+  uint32_t block;   // MIN / MAX scans: > 0 restarts the scan at every block of this many positions
   const uint32_t* bits;  // word scans: the bitmap
   const void* in;        // position scans: the input column
   const uint8_t* in_valid;
@@ -73,10 +80,14 @@ struct WinCommon {
 struct WinEvalFn {
   int32_t fn, frame, in_type, out_width;
   int64_t offset;
+  int64_t lo, hi;  // QE_FRAME_ROWS_BETWEEN: the bounds, clamped to [-n, n]
+  int64_t block;   // MIN / MAX: the block length of its scans (0: none)
   const void* in;
   const uint8_t* in_valid;
-  const int64_t* scan_v;
+  const int64_t* scan_v;  // the forward scan (SUM / COUNT: the running pair)
   const int32_t* scan_f;
+  const int64_t* back_v;  // MIN / MAX: the backward scan
+  const int32_t* back_f;
   void* out;
   uint32_t* out_valid;
 };
@@ -92,6 +103,7 @@ struct WinArgs {
   WinJob jobs[WIN_MAX_JOBS];
   WinEvalFn fns[QE_MAX_AGGS];
 };
+static_assert(sizeof(WinArgs) <= 4096, "WinArgs is passed by value: the kernel-argument segment holds 4 KiB");
 
 // ---- bitmap words -----------------------------------------------------------------------------------
 // Word w of a boundary bitmap as the scans read it: bits at and past n cleared, bit 0 of word 0 set
@@ -129,7 +141,30 @@ __device__ __forceinline__ WinElem win_identity(int32_t src) {
   return e;
 }
 
-// a then b (a covers the earlier elements). Associative for every src; not commutative for MIN / MAX.
+// MIN / MAX of the rows of l followed by the rows of h, l the earlier in WINDOW order (the flags
+// without WF_RESET). Associative, not commutative: the first non-null value seeds the NaN, and of equal
+// values the earlier stays.
+__device__ __forceinline__ WinElem win_merge(bool is_max, int32_t in_type, const WinElem& l, const WinElem& h) {
+  WinElem r;
+  r.pad = 0;
+  r.f = ((l.f | h.f) & (WF_HAS | WF_HASNUM)) | (((l.f & WF_HAS) ? l.f : h.f) & WF_SEEDNAN);
+  if ((l.f & WF_HASNUM) && (h.f & WF_HASNUM)) {
+    bool take_h;  // strictly better only: the earlier of equal values stays (-0.0 == +0.0)
+    if (in_type == QE_TYPE_FLOAT64) {
+      const double x = __longlong_as_double(l.v), y = __longlong_as_double(h.v);
+      take_h = is_max ? y > x : y < x;
+    } else {
+      take_h = is_max ? h.v > l.v : h.v < l.v;
+    }
+    r.v = take_h ? h.v : l.v;
+  } else {
+    r.v = (l.f & WF_HASNUM) ? l.v : h.v;
+  }
+  return r;
+}
+
+// a then b in SCAN order (a covers the elements scanned earlier). Associative for every src; not
+// commutative for MIN / MAX.
 __device__ __forceinline__ WinElem win_combine(const WinJob& J, const WinElem& a, const WinElem& b) {
   WinElem r;
   r.pad = 0;
@@ -149,22 +184,15 @@ __device__ __forceinline__ WinElem win_combine(const WinJob& J, const WinElem& a
       return r;
     default: break;
   }
-  if (b.f & WF_RESET) return b;  // b starts a partition: nothing before it counts
-  r.f = ((a.f | b.f) & (WF_HAS | WF_HASNUM)) | (((a.f & WF_HAS) ? a.f : b.f) & WF_SEEDNAN) | (a.f & WF_RESET);
-  if ((a.f & WF_HASNUM) && (b.f & WF_HASNUM)) {
-    bool take_b;  // strictly better only: the earlier of equal values stays (-0.0 == +0.0)
-    if (J.in_type == QE_TYPE_FLOAT64) {
-      const double x = __longlong_as_double(a.v), y = __longlong_as_double(b.v);
-      take_b = J.src == WS_MAX ? y > x : y < x;
-    } else {
-      take_b = J.src == WS_MAX ? b.v > a.v : b.v < a.v;
-    }
-    r.v = take_b ? b.v : a.v;
-  } else {
-    r.v = (a.f & WF_HASNUM) ? a.v : b.v;
-  }
+  if (b.f & WF_RESET) return b;  // b starts a segment: nothing scanned before it counts
+  // a backward scan meets the window-later rows first: b is then the window-earlier operand
+  r = J.back ? win_merge(J.src == WS_MAX, J.in_type, b, a) : win_merge(J.src == WS_MAX, J.in_type, a, b);
+  r.f |= a.f & WF_RESET;
   return r;
 }
+
+// Where element k (< count) of a position scan lives: its position.
+__device__ __forceinline__ int64_t win_slot(const WinJob& J, int64_t k) { return J.back ? J.count - 1 - k : k; }
 
 // Element k of a job (the identity past its count).
 __device__ __forceinline__ WinElem win_load(const WinJob& J, const WinCommon& C, int64_t k) {
@@ -185,7 +213,8 @@ __device__ __forceinline__ WinElem win_load(const WinJob& J, const WinCommon& C,
     case WS_POPC: e.v = __popc(win_word(J.bits, k, C.n)); return e;
     default: break;
   }
-  const int64_t r = C.order[k];
+  const int64_t p = win_slot(J, k);
+  const int64_t r = C.order[p];
   const bool valid = (uint64_t)r < (uint64_t)C.n && row_valid(J.in_valid, r);
   const int64_t v = valid ? win_value(J.in_type, J.in, r) : 0;
   if (J.src == WS_SUM) {
@@ -196,7 +225,15 @@ __device__ __forceinline__ WinElem win_load(const WinJob& J, const WinCommon& C,
   const bool nan = valid && J.in_type == QE_TYPE_FLOAT64 && win_is_nan(v);
   e.v = nan ? 0 : v;
   e.f = valid ? (WF_HAS | (nan ? WF_SEEDNAN : WF_HASNUM)) : 0;
-  if (k == 0 || ((C.part[k >> 5] >> (k & 31)) & 1)) e.f |= WF_RESET;
+  // a segment starts at a partition's first position and at a block's (backward: at their last)
+  bool reset;
+  if (!J.back) {
+    reset = p == 0 || ((C.part[p >> 5] >> (p & 31)) & 1) || (J.block && (uint32_t)p % J.block == 0);
+  } else {
+    const int64_t q = p + 1;
+    reset = q == C.n || ((C.part[q >> 5] >> (q & 31)) & 1) || (J.block && (uint32_t)q % J.block == 0);
+  }
+  if (reset) e.f |= WF_RESET;
   return e;
 }
 
@@ -206,9 +243,11 @@ __device__ __forceinline__ void win_store(const WinJob& J, int64_t k, const WinE
     case WS_PREV:
     case WS_POPC: J.out_f[k] = (int32_t)e.v; break;
     case WS_NEXT: J.out_f[J.count - 1 - k] = (int32_t)e.v; break;
-    default:
-      J.out_v[k] = e.v;
-      J.out_f[k] = e.f;
+    default: {
+      const int64_t p = win_slot(J, k);
+      J.out_v[p] = e.v;
+      J.out_f[p] = e.f;
+    }
   }
 }
 
@@ -265,8 +304,9 @@ __device__ __forceinline__ WinElem win_scan_tile(const WinJob& J, const WinCommo
     for (int j = 0; j < WIN_ITEMS; ++j) {
       x[j] = win_identity(J.src);
       if (k0 + j < J.count) {
-        x[j].v = J.out_v[k0 + j];
-        x[j].f = J.out_f[k0 + j];
+        const int64_t p = win_slot(J, k0 + j);
+        x[j].v = J.out_v[p];
+        x[j].f = J.out_f[p];
       }
     }
   } else {
@@ -317,26 +357,62 @@ __device__ __forceinline__ void win_eval_pos(const WinArgs& A, int64_t i, int64_
   uint64_t valid_bits = 0;
   for (int k = 0; k < A.nfns; ++k) {
     const WinEvalFn& F = A.fns[k];
-    const int64_t e = F.frame == QE_FRAME_ROWS ? i : F.frame == QE_FRAME_RANGE ? Ge : Pe;
+    // the frame [s, e] (nothing is read at s or e while it is empty)
+    int64_t s = P, e = F.frame == QE_FRAME_ROWS ? i : F.frame == QE_FRAME_RANGE ? Ge : Pe;
+    bool empty = false;
+    if (F.frame == QE_FRAME_ROWS_BETWEEN) {  // the bounds are compared, never added before that
+      empty = F.lo > F.hi || F.lo > Pe - i || F.hi < P - i;
+      s = empty || F.lo <= P - i ? P : i + F.lo;
+      e = empty ? P : F.hi >= Pe - i ? Pe : i + F.hi;
+    }
     int64_t val = 0;
     bool valid = true;
     switch (F.fn) {
       case QE_WIN_ROW_NUMBER: val = i - P + 1; break;
       case QE_WIN_RANK: val = G - P + 1; break;
       case QE_WIN_DENSE_RANK: val = dense; break;
-      case QE_WIN_COUNT_STAR: val = e - P + 1; break;
-      case QE_WIN_COUNT: val = (int64_t)F.scan_f[e] - (P ? (int64_t)F.scan_f[P - 1] : 0); break;
+      case QE_WIN_COUNT_STAR: val = empty ? 0 : e - s + 1; break;
+      case QE_WIN_COUNT: val = empty ? 0 : (int64_t)F.scan_f[e] - (s ? (int64_t)F.scan_f[s - 1] : 0); break;
       case QE_WIN_SUM: {
-        const int64_t cnt = (int64_t)F.scan_f[e] - (P ? (int64_t)F.scan_f[P - 1] : 0);
+        const int64_t cnt = empty ? 0 : (int64_t)F.scan_f[e] - (s ? (int64_t)F.scan_f[s - 1] : 0);
         valid = cnt > 0;
-        if (valid) val = (int64_t)((uint64_t)F.scan_v[e] - (P ? (uint64_t)F.scan_v[P - 1] : 0ull));
+        if (valid) val = (int64_t)((uint64_t)F.scan_v[e] - (s ? (uint64_t)F.scan_v[s - 1] : 0ull));
         break;
       }
       case QE_WIN_MIN:
       case QE_WIN_MAX: {
-        const int32_t fl = F.scan_f[e];
-        valid = (fl & WF_HAS) != 0;
-        if (valid) val = (fl & WF_SEEDNAN) ? WIN_CANON_NAN : F.scan_v[e];
+        // The forward scan at e covers [max(P, e's block start), e], the backward scan at s covers
+        // [s, min(Pe, s's block end)], and a frame is at most one block long: it straddles one block
+        // edge (both halves), or starts where the forward scan's segment starts, or ends where the
+        // backward scan's segment ends (a frame strictly inside a block is clipped at Pe, or it would
+        // be the whole block). Without a block length the only edges are the partition's.
+        valid = false;
+        if (empty) break;
+        const int64_t bs = F.block ? e - (int64_t)((uint32_t)e % (uint32_t)F.block) : 0;
+        WinElem r;
+        if (s < bs) {
+          WinElem l, h;
+          l.v = F.back_v[s], l.f = F.back_f[s], l.pad = 0;
+          h.v = F.scan_v[e], h.f = F.scan_f[e], h.pad = 0;
+          r = win_merge(F.fn == QE_WIN_MAX, F.in_type, l, h);
+        } else if (F.scan_f && (s == P || s == bs)) {
+          r.v = F.scan_v[e], r.f = F.scan_f[e];
+        } else {
+          r.v = F.back_v[s], r.f = F.back_f[s];
+        }
+        valid = (r.f & WF_HAS) != 0;
+        if (valid) val = (r.f & WF_SEEDNAN) ? WIN_CANON_NAN : r.v;
+        break;
+      }
+      case QE_WIN_FIRST_VALUE:
+      case QE_WIN_LAST_VALUE: {
+        valid = false;
+        if (empty) break;
+        const int64_t rr = C.order[F.fn == QE_WIN_FIRST_VALUE ? s : e];
+        if ((uint64_t)rr < (uint64_t)n && row_valid(F.in_valid, rr)) {
+          valid = true;
+          val = win_value(F.in_type, F.in, rr);
+        }
         break;
       }
       default: {  // LAG / LEAD: the offset is compared as an int64, never added before that
@@ -647,8 +723,12 @@ int qe_window_boundaries(qe_ctx* ctx, const qe_column* keys, int32_t nkeys, cons
   return launch_check("k_win_boundaries");
 }
 
-int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_starts, const qe_column* peer_starts,
-                   const qe_column* inputs, int32_t ninputs, const qe_window_fn* fns, int32_t nfns, qe_column* outs) {
+}  // extern "C"
+
+// qe_window_eval (frames_call false: window_check's ids, bounds null) and qe_window_eval_frames.
+static int window_eval_impl(qe_ctx* ctx, const qe_column* order, const qe_column* part_starts, const qe_column* peer_starts,
+                            const qe_column* inputs, int32_t ninputs, const qe_window_fn* fns, const qe_window_bounds* bounds,
+                            int32_t nfns, qe_column* outs, bool frames_call) {
   QE_TRY(ctx_enter(ctx));
   QE_CHECK(part_starts != nullptr, QE_ERR_INVALID_ARG, "window_eval: null partition starts column");
   const int64_t n = part_starts->length;
@@ -665,13 +745,15 @@ int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_st
   WinArgs A{};
   for (int k = 0; k < nfns; ++k) {
     const qe_window_fn& f = fns[k];
-    QE_CHECK(window_fn_known(f.fn), QE_ERR_INVALID_ARG, "window_eval: function %d: unknown function %d", k, f.fn);
-    const bool has_in = window_takes_input(f.fn);
+    QE_CHECK(frames_call ? window_frames_fn_known(f.fn) : window_fn_known(f.fn), QE_ERR_INVALID_ARG,
+             "window_eval: function %d: unknown function %d", k, f.fn);
+    const bool has_in = window_frames_takes_input(f.fn);
     QE_CHECK(!has_in || (f.input >= 0 && f.input < ninputs), QE_ERR_INVALID_ARG, "window_eval: function %d: input %d outside [0, %d)",
              k, f.input, ninputs);
     const qe_column* in = has_in ? &inputs[f.input] : nullptr;
     int32_t out_type;
-    const int st = window_check(f.fn, f.frame, in ? in->type : 0, f.offset, &out_type);
+    const int st = frames_call ? window_frames_check(f.fn, f.frame, in ? in->type : 0, f.offset, bounds != nullptr, &out_type)
+                               : window_check(f.fn, f.frame, in ? in->type : 0, f.offset, &out_type);
     QE_CHECK(st == QE_OK, st, "window_eval: function %d (fn %d, frame %d, input type %d, offset %lld) is %s", k, f.fn, f.frame,
              in ? in->type : 0, (long long)f.offset, st == QE_ERR_UNSUPPORTED ? "not supported" : "not valid");
     const bool reads = has_in && f.fn != QE_WIN_COUNT;
@@ -680,7 +762,7 @@ int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_st
     QE_CHECK(o.type == out_type, QE_ERR_INVALID_ARG, "window_eval: output %d must have type %d, has %d", k, out_type, o.type);
     QE_CHECK(o.length >= n, QE_ERR_CAPACITY, "window_eval: output %d holds %lld rows, need %lld", k, (long long)o.length, (long long)n);
     QE_CHECK(o.values || n == 0, QE_ERR_INVALID_ARG, "window_eval: output %d has no values", k);
-    QE_CHECK((o.validity || !window_nullable(f.fn)) && ((uintptr_t)o.validity & 3) == 0, QE_ERR_INVALID_ARG,
+    QE_CHECK((o.validity || !window_frames_nullable(f.fn)) && ((uintptr_t)o.validity & 3) == 0, QE_ERR_INVALID_ARG,
              "window_eval: output %d needs a 4-byte aligned validity buffer (its result can be null)", k);
     WinEvalFn& F = A.fns[k];
     F.fn = f.fn;
@@ -688,6 +770,10 @@ int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_st
     F.in_type = in ? in->type : 0;
     F.out_width = type_width(out_type);
     F.offset = f.offset;
+    if (f.frame == QE_FRAME_ROWS_BETWEEN) {
+      F.lo = window_clamp_bound(bounds[k].lo, n);
+      F.hi = window_clamp_bound(bounds[k].hi, n);
+    }
     F.in = in ? in->values : nullptr;
     F.in_valid = in ? in->validity : nullptr;
     F.out = o.values;
@@ -697,11 +783,11 @@ int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_st
   for (int k = 0; k < nfns; ++k) outs[k].length = n;
   if (n == 0 || nfns == 0) return QE_OK;
 
-  const WindowScans S = window_scans(fns, nfns);
+  const WindowFrameScans S = window_frame_scans(fns, bounds, nfns, n);
   const int64_t nw = window_words(n), tiles = window_tiles(n);
   Blocks blk(ctx);
   char* p;
-  QE_TRY(blk.alloc((size_t)window_work_bytes(n, S.n, nfns), (void**)&p));
+  QE_TRY(blk.alloc((size_t)window_frames_work_bytes(n, fns, bounds, nfns), (void**)&p));
   A.c = WinCommon{(const int32_t*)order->values, (const uint32_t*)part_starts->values, (const uint32_t*)peer_starts->values, n, nw,
                   nullptr, (unsigned*)p};
   p += WIN_HEAD_BYTES;
@@ -716,7 +802,7 @@ int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_st
   A.cum_peer = words[4];
   const int32_t word_src[WIN_WORD_SCANS] = {WS_PREV, WS_NEXT, WS_PREV, WS_NEXT, WS_POPC};
   for (int j = 0; j < WIN_WORD_SCANS; ++j)
-    A.jobs[j] = WinJob{word_src[j], 0, j < 2 ? A.c.part : A.c.peer, nullptr, nullptr, nw, nullptr, words[j]};
+    A.jobs[j] = WinJob{word_src[j], 0, 0, 0, j < 2 ? A.c.part : A.c.peer, nullptr, nullptr, nw, nullptr, words[j]};
   A.njobs = WIN_WORD_SCANS + S.n;
   A.nfns = nfns;
   for (int j = 0; j < S.n; ++j) {
@@ -726,13 +812,20 @@ int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_st
     int32_t* f = (int32_t*)p;
     p += window_scan_flag_bytes(n);
     const int32_t src = S.kind[j] == WIN_SCAN_SUM ? WS_SUM : S.kind[j] == WIN_SCAN_MIN ? WS_MIN : WS_MAX;
-    A.jobs[WIN_WORD_SCANS + j] = WinJob{src, in.type, nullptr, in.values, in.validity, n, v, f};
+    A.jobs[WIN_WORD_SCANS + j] = WinJob{src, in.type, S.back[j], (uint32_t)S.block[j], nullptr, in.values, in.validity, n, v, f};
   }
-  for (int k = 0; k < nfns; ++k)
-    if (S.of_fn[k] >= 0) {
-      A.fns[k].scan_v = A.jobs[WIN_WORD_SCANS + S.of_fn[k]].out_v;
-      A.fns[k].scan_f = A.jobs[WIN_WORD_SCANS + S.of_fn[k]].out_f;
+  for (int k = 0; k < nfns; ++k) {
+    if (S.fwd_of_fn[k] >= 0) {
+      A.fns[k].scan_v = A.jobs[WIN_WORD_SCANS + S.fwd_of_fn[k]].out_v;
+      A.fns[k].scan_f = A.jobs[WIN_WORD_SCANS + S.fwd_of_fn[k]].out_f;
+      A.fns[k].block = S.block[S.fwd_of_fn[k]];
     }
+    if (S.bwd_of_fn[k] >= 0) {
+      A.fns[k].back_v = A.jobs[WIN_WORD_SCANS + S.bwd_of_fn[k]].out_v;
+      A.fns[k].back_f = A.jobs[WIN_WORD_SCANS + S.bwd_of_fn[k]].out_f;
+      A.fns[k].block = S.block[S.bwd_of_fn[k]];
+    }
+  }
   A.tile_agg = (WinElem*)p;
   p += window_tile_bytes(n, S.n);
   A.tile_carry = (WinElem*)p;
@@ -767,6 +860,19 @@ int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_st
   QE_TRY(ctx_sync(ctx));
   QE_CHECK(*(const unsigned*)hp == 0, QE_ERR_INVALID_ARG, "window_eval: an order entry is outside [0, %lld)", (long long)n);
   return QE_OK;
+}
+
+extern "C" {
+
+int qe_window_eval(qe_ctx* ctx, const qe_column* order, const qe_column* part_starts, const qe_column* peer_starts,
+                   const qe_column* inputs, int32_t ninputs, const qe_window_fn* fns, int32_t nfns, qe_column* outs) {
+  return window_eval_impl(ctx, order, part_starts, peer_starts, inputs, ninputs, fns, nullptr, nfns, outs, false);
+}
+
+int qe_window_eval_frames(qe_ctx* ctx, const qe_column* order, const qe_column* part_starts, const qe_column* peer_starts,
+                          const qe_column* inputs, int32_t ninputs, const qe_window_fn* fns, const qe_window_bounds* bounds,
+                          int32_t nfns, qe_column* outs) {
+  return window_eval_impl(ctx, order, part_starts, peer_starts, inputs, ninputs, fns, bounds, nfns, outs, true);
 }
 
 }  // extern "C"

@@ -1,8 +1,10 @@
 // qe_window_plan.hpp — the host-side rules of the window functions as plain
 // functions of numbers: which function x type x frame combinations qe_window_eval accepts and with
 // which status it refuses the others, the output types, which scan over the sorted positions each
-// function reads, and the working memory of a call. Plain C++17: qe_window.hip uses them and keeps no
-// second copy, and tests/native/window_plan_host.cpp (g++) holds them to tests/windowref.py without a
+// function reads, and the working memory of a call; then the same for qe_window_eval_frames (two more
+// functions, the frame ROWS BETWEEN lo AND hi, forward and backward block scans). Plain C++17:
+// qe_window.hip uses them and keeps no second copy, and tests/native/window_plan_host.cpp and
+// window_frames_host.cpp (g++) hold them to tests/windowref.py and tests/windowframeref.py without a
 // GPU.
 #pragma once
 
@@ -119,6 +121,96 @@ inline int64_t window_work_bytes(int64_t n, int32_t nscans, int32_t nfns) {
   return WIN_HEAD_BYTES + window_inv_bytes(n) + WIN_WORD_SCANS * window_word_bytes(n) +
          (int64_t)nscans * (window_scan_value_bytes(n) + window_scan_flag_bytes(n)) + 2 * window_tile_bytes(n, nscans) +
          window_stage_bytes(n, nfns);
+}
+
+// ---- qe_window_eval_frames: FIRST_VALUE / LAST_VALUE and the QE_FRAME_ROWS_BETWEEN frame ---------------
+// The rules above widened by two functions and one frame; qe_window_eval keeps the rules above.
+inline bool window_frames_fn_known(int32_t fn) { return fn >= QE_WIN_ROW_NUMBER && fn <= QE_WIN_LAST_VALUE; }
+inline bool window_frames_frame_known(int32_t frame) { return frame >= QE_FRAME_ROWS && frame <= QE_FRAME_ROWS_BETWEEN; }
+inline bool window_frames_takes_input(int32_t fn) { return fn >= QE_WIN_COUNT && fn <= QE_WIN_LAST_VALUE; }
+inline bool window_frames_nullable(int32_t fn) { return fn >= QE_WIN_SUM && fn <= QE_WIN_LAST_VALUE; }
+
+// window_check for the wider ids. has_bounds: the call passed a bounds array (QE_FRAME_ROWS_BETWEEN
+// needs one, whatever the function; the bounds' values are never a reason to refuse).
+inline int window_frames_check(int32_t fn, int32_t frame, int32_t in_type, int64_t offset, bool has_bounds, int32_t* out_type) {
+  *out_type = 0;
+  if (!window_frames_fn_known(fn) || !window_frames_frame_known(frame)) return QE_ERR_INVALID_ARG;
+  if (frame == QE_FRAME_ROWS_BETWEEN && !has_bounds) return QE_ERR_INVALID_ARG;
+  if (fn == QE_WIN_FIRST_VALUE || fn == QE_WIN_LAST_VALUE) {  // the types LAG takes; no offset
+    if (!window_type_known(in_type)) return QE_ERR_INVALID_ARG;
+    if (!window_type_value(in_type)) return QE_ERR_UNSUPPORTED;
+    *out_type = in_type;
+    return QE_OK;
+  }
+  return window_check(fn, frame == QE_FRAME_ROWS_BETWEEN ? QE_FRAME_ROWS : frame, in_type, offset, out_type);
+}
+
+// A bound clamped to [-n, n]: no frame changes (a partition has at most n rows, so i + lo < P for every
+// lo <= -n and i + lo > Pe for every lo >= n, and likewise for hi), and hi - lo + 1 cannot overflow.
+inline int64_t window_clamp_bound(int64_t b, int64_t n) { return b < -n ? -n : b > n ? n : b; }
+
+// The scans over positions of a qe_window_eval_frames call. A scan is (kind, input, direction, block
+// length): forward scans restart where a partition starts and, with a block length L > 0, where
+// position % L == 0; backward scans run from the right and restart where a partition ends and where
+// position % L == L - 1. Block length 0: partitions only. (kind, input, forward, 0) is the scan of
+// window_scans, so a call without bounded MIN / MAX has window_scans' list.
+//   SUM / COUNT(x), any frame: the running pair, forward, 0 (a frame's value is S[e] - S[s-1]).
+//   MIN / MAX under the three older frames: forward, 0.
+//   MIN / MAX under QE_FRAME_ROWS_BETWEEN, (lo, hi) clamped to [-n, n]:
+//     lo > hi            every frame is empty: no scan
+//     lo == -n           s = P for every row: forward, 0, read at e
+//     hi == n            e = Pe for every row: backward, 0, read at s
+//     otherwise          L = hi - lo + 1 bounds a frame's width: forward and backward with block length L,
+//                        or 0 when L >= n (one block would cover every position)
+struct WindowFrameScans {
+  int32_t n = 0;
+  int32_t kind[2 * QE_MAX_AGGS] = {};
+  int32_t input[2 * QE_MAX_AGGS] = {};
+  int32_t back[2 * QE_MAX_AGGS] = {};
+  int64_t block[2 * QE_MAX_AGGS] = {};
+  int32_t fwd_of_fn[QE_MAX_AGGS] = {};  // index of the forward scan function k reads, -1 when none
+  int32_t bwd_of_fn[QE_MAX_AGGS] = {};  // ... of the backward scan
+};
+
+inline int32_t window_frame_scan_slot(WindowFrameScans& S, int32_t kind, int32_t input, int32_t back, int64_t block) {
+  for (int32_t j = 0; j < S.n; ++j)
+    if (S.kind[j] == kind && S.input[j] == input && S.back[j] == back && S.block[j] == block) return j;
+  S.kind[S.n] = kind;
+  S.input[S.n] = input;
+  S.back[S.n] = back;
+  S.block[S.n] = block;
+  return S.n++;
+}
+
+// bounds may be null when no function has frame QE_FRAME_ROWS_BETWEEN.
+inline WindowFrameScans window_frame_scans(const qe_window_fn* fns, const qe_window_bounds* bounds, int32_t nfns, int64_t n) {
+  WindowFrameScans S;
+  for (int32_t k = 0; k < nfns && k < QE_MAX_AGGS; ++k) {
+    const int32_t kind = window_scan_of(fns[k].fn);
+    S.fwd_of_fn[k] = S.bwd_of_fn[k] = -1;
+    if (kind == WIN_SCAN_NONE) continue;
+    if (kind == WIN_SCAN_SUM || fns[k].frame != QE_FRAME_ROWS_BETWEEN || !bounds) {
+      S.fwd_of_fn[k] = window_frame_scan_slot(S, kind, fns[k].input, 0, 0);
+      continue;
+    }
+    const int64_t lo = window_clamp_bound(bounds[k].lo, n), hi = window_clamp_bound(bounds[k].hi, n);
+    if (lo > hi) continue;
+    if (lo == -n) {
+      S.fwd_of_fn[k] = window_frame_scan_slot(S, kind, fns[k].input, 0, 0);
+    } else if (hi == n) {
+      S.bwd_of_fn[k] = window_frame_scan_slot(S, kind, fns[k].input, 1, 0);
+    } else {
+      const int64_t L = hi - lo + 1, block = L >= n ? 0 : L;
+      S.fwd_of_fn[k] = window_frame_scan_slot(S, kind, fns[k].input, 0, block);
+      S.bwd_of_fn[k] = window_frame_scan_slot(S, kind, fns[k].input, 1, block);
+    }
+  }
+  return S;
+}
+
+// Working memory of a qe_window_eval_frames call: window_work_bytes with this call's scans.
+inline int64_t window_frames_work_bytes(int64_t n, const qe_window_fn* fns, const qe_window_bounds* bounds, int32_t nfns) {
+  return window_work_bytes(n, window_frame_scans(fns, bounds, nfns, n).n, nfns);
 }
 
 }  // namespace qe

@@ -374,23 +374,28 @@ class AvgExpression(AggregateExpression):
 # ---- window expressions: fn(...) OVER (PARTITION BY ... ORDER BY ...) (build-defined) ----
 class WindowExpression:
     """One function of a WindowExec. expr: the input expression (None for the functions without
-    one); frame: N.FRAME_ROWS / FRAME_RANGE / FRAME_PARTITION (read by the aggregates only; every
-    frame starts at the partition's first row); offset: LAG / LEAD."""
+    one); frame: N.FRAME_ROWS / FRAME_RANGE / FRAME_PARTITION (read by the aggregates and FIRST / LAST
+    only; these frames start at the partition's first row); offset: LAG / LEAD; bounds: (lo, hi) makes
+    the frame ROWS BETWEEN lo AND hi (N.FRAME_ROWS_BETWEEN), offsets in rows from the current row,
+    negative PRECEDING, N.UNBOUNDED_PRECEDING / N.UNBOUNDED_FOLLOWING at the ends."""
 
     fn: int = 0
     name: str = "?"
 
-    def __init__(self, expr: Optional[Expression] = None, frame: int = N.FRAME_RANGE, offset: int = 0):
+    def __init__(self, expr: Optional[Expression] = None, frame: int = N.FRAME_RANGE, offset: int = 0, bounds=None):
         self.expr = expr
-        self.frame = int(frame)
+        self.frame = int(frame) if bounds is None else N.FRAME_ROWS_BETWEEN
         self.offset = int(offset)
+        self.bounds = None if bounds is None else (int(bounds[0]), int(bounds[1]))
 
     def inputExpression(self) -> Optional[Expression]:  # noqa: N802
         return self.expr
 
     def output_type(self, input_type: Optional[int]) -> int:
-        """INT64 for the ranks, the counts and SUM; the input's type for MIN / MAX / LAG / LEAD."""
-        return input_type if self.fn in (N.WIN_MIN, N.WIN_MAX, N.WIN_LAG, N.WIN_LEAD) else N.TYPE_INT64
+        """INT64 for the ranks, the counts and SUM; the input's type for MIN / MAX / LAG / LEAD / FIRST_VALUE /
+        LAST_VALUE."""
+        by_input = (N.WIN_MIN, N.WIN_MAX, N.WIN_LAG, N.WIN_LEAD, N.WIN_FIRST_VALUE, N.WIN_LAST_VALUE)
+        return input_type if self.fn in by_input else N.TYPE_INT64
 
     def __repr__(self) -> str:
         return f"{self.name}({self.expr if self.expr is not None else ''})"
@@ -416,16 +421,16 @@ class WindowCount(WindowExpression):
 
     name = "COUNT"
 
-    def __init__(self, expr: Optional[Expression] = None, frame: int = N.FRAME_RANGE):
-        super().__init__(expr, frame)
+    def __init__(self, expr: Optional[Expression] = None, frame: int = N.FRAME_RANGE, bounds=None):
+        super().__init__(expr, frame, bounds=bounds)
         self.fn = N.WIN_COUNT_STAR if expr is None else N.WIN_COUNT
 
 
 class WindowSum(WindowExpression):
     fn, name = N.WIN_SUM, "SUM"
 
-    def __init__(self, expr: Expression, frame: int = N.FRAME_RANGE):
-        super().__init__(expr, frame)
+    def __init__(self, expr: Expression, frame: int = N.FRAME_RANGE, bounds=None):
+        super().__init__(expr, frame, bounds=bounds)
 
 
 class WindowMin(WindowSum):
@@ -434,6 +439,16 @@ class WindowMin(WindowSum):
 
 class WindowMax(WindowSum):
     fn, name = N.WIN_MAX, "MAX"
+
+
+class FirstValue(WindowSum):
+    """x of the frame's first row, nulls included; null when the frame is empty."""
+
+    fn, name = N.WIN_FIRST_VALUE, "FIRST_VALUE"
+
+
+class LastValue(WindowSum):
+    fn, name = N.WIN_LAST_VALUE, "LAST_VALUE"
 
 
 class Lag(WindowExpression):

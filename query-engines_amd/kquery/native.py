@@ -50,10 +50,14 @@ SORT_DESC, SORT_NULLS_FIRST = 1, 2  # qe_sort_indices flag bits (0: ascending, n
 TOPK_AUTO, TOPK_SELECT, TOPK_SORT = 0, 1, 2  # qe_topk_indices modes
 JOIN_INNER, JOIN_LEFT = 0, 1  # qe_join_probe kinds
 JOIN_TRACK = 0x100  # OR-ed into a kind: the probe also marks the build keys it matches
-# qe_window_eval functions and frames (every frame starts at the partition's first row)
+# qe_window_eval functions and frames (these three frames start at the partition's first row)
 (WIN_ROW_NUMBER, WIN_RANK, WIN_DENSE_RANK, WIN_COUNT_STAR, WIN_COUNT, WIN_SUM, WIN_MIN, WIN_MAX, WIN_LAG,
  WIN_LEAD) = range(1, 11)
 FRAME_ROWS, FRAME_RANGE, FRAME_PARTITION = 0, 1, 2
+# qe_window_eval_frames only: two more functions, and ROWS BETWEEN lo AND hi (offsets from the current row)
+WIN_FIRST_VALUE, WIN_LAST_VALUE = 11, 12
+FRAME_ROWS_BETWEEN = 3
+UNBOUNDED_PRECEDING, UNBOUNDED_FOLLOWING = -2**63, 2**63 - 1
 
 MAX_KEYS, MAX_AGGS, MAX_COLS, MAX_TERMS, MAX_TOKENS = 4, 8, 8, 8, 16
 TOK_COL, TOK_LIT, TOK_ADD, TOK_SUB, TOK_MUL, TOK_DIV = 1, 2, 3, 4, 5, 6
@@ -142,6 +146,10 @@ class QeAggDesc(C.Structure):
 class QeWindowFn(C.Structure):
     _fields_ = [("fn", C.c_int32), ("frame", C.c_int32), ("input", C.c_int32), ("reserved", C.c_int32),
                 ("offset", C.c_int64)]
+
+
+class QeWindowBounds(C.Structure):
+    _fields_ = [("lo", C.c_int64), ("hi", C.c_int64)]
 
 
 class QePredTerm(C.Structure):
@@ -257,6 +265,8 @@ SIGNATURES = [
     ("qe_topk_last_stats", C.c_int, [_P, _I64P]),
     ("qe_window_boundaries", C.c_int, [_P, _COLP, C.c_int32, _COLP, _COLP]),
     ("qe_window_eval", C.c_int, [_P, _COLP, _COLP, _COLP, _COLP, C.c_int32, C.POINTER(QeWindowFn), C.c_int32, _COLP]),
+    ("qe_window_eval_frames", C.c_int, [_P, _COLP, _COLP, _COLP, _COLP, C.c_int32, C.POINTER(QeWindowFn),
+                                        C.POINTER(QeWindowBounds), C.c_int32, _COLP]),
     ("qe_window_layout", C.c_int, [C.POINTER(C.c_int32), C.POINTER(C.c_int32)]),
     ("qe_join_build", C.c_int, [_P, _COLP, _PP]),
     ("qe_join_destroy", C.c_int, [_P]),

@@ -306,8 +306,8 @@ def _take(indices: DeviceColumn, cols: Sequence[DeviceColumn], utf8_bytes, or_nu
 # ---------------------------------------------------------------------------------------------------
 # Window functions (build-defined): run boundaries along a sort, scans, per-row evaluation
 # ---------------------------------------------------------------------------------------------------
-_WIN_NULLABLE = (N.WIN_SUM, N.WIN_MIN, N.WIN_MAX, N.WIN_LAG, N.WIN_LEAD)
-_WIN_INPUT_TYPE = (N.WIN_MIN, N.WIN_MAX, N.WIN_LAG, N.WIN_LEAD)
+_WIN_NULLABLE = (N.WIN_SUM, N.WIN_MIN, N.WIN_MAX, N.WIN_LAG, N.WIN_LEAD, N.WIN_FIRST_VALUE, N.WIN_LAST_VALUE)
+_WIN_INPUT_TYPE = (N.WIN_MIN, N.WIN_MAX, N.WIN_LAG, N.WIN_LEAD, N.WIN_FIRST_VALUE, N.WIN_LAST_VALUE)
 
 
 def window_layout():
@@ -347,12 +347,36 @@ def window_eval(order: DeviceColumn, part_starts: DeviceColumn, peer_starts: Dev
     return list(outs)
 
 
+def window_eval_frames(order: DeviceColumn, part_starts: DeviceColumn, peer_starts: DeviceColumn,
+                       inputs: Sequence[DeviceColumn], fns, outs: Optional[Sequence[DeviceColumn]] = None,
+                       pass_bounds: bool = True) -> List[DeviceColumn]:
+    """qe_window_eval_frames: fns is a sequence of (fn, frame, input index, offset, lo, hi), lo and hi
+    the bounds of a FRAME_ROWS_BETWEEN frame (any int64; ignored under the other frames); otherwise as
+    window_eval. pass_bounds=False passes a null bounds array."""
+    ctx = order.ctx
+    n = part_starts.length
+    if outs is None:
+        outs = []
+        for fn, _, inp, _, _, _ in fns:
+            t = inputs[inp].type if fn in _WIN_INPUT_TYPE and 0 <= inp < len(inputs) else N.TYPE_INT64
+            outs.append(DeviceColumn.empty(t if t in N.FIXED_WIDTH else N.TYPE_INT64, n, fn in _WIN_NULLABLE, ctx=ctx))
+    fc = (N.QeWindowFn * max(len(fns), 1))(*[N.QeWindowFn(int(fn), int(fr), int(inp), 0, int(off)) for fn, fr, inp, off, _, _ in fns])
+    bc = (N.QeWindowBounds * max(len(fns), 1))(*[N.QeWindowBounds(int(lo), int(hi)) for _, _, _, _, lo, hi in fns])
+    ic = (N.QeColumn * max(len(inputs), 1))(*[c.as_c() for c in inputs])
+    oc = (N.QeColumn * max(len(outs), 1))(*[o.as_c() for o in outs])
+    rc, pc, gc = order.as_c(), part_starts.as_c(), peer_starts.as_c()
+    N.check(N.lib().qe_window_eval_frames(ctx.handle, N.C.byref(rc), N.C.byref(pc), N.C.byref(gc), ic, len(inputs), fc,
+                                          bc if pass_bounds else None, len(fns), oc))
+    return list(outs)
+
+
 class WindowExec(PhysicalPlan):
     """fn(...) OVER (PARTITION BY ... ORDER BY ...) (build-defined). A pipeline breaker like
     SortExec: drains its input into one batch (concat_batches), evaluates the key and input
     expressions, sorts by (partition keys ascending, then order keys) to row indices
     (qe_sort_indices), finds the partition and peer boundaries along them (qe_window_boundaries,
-    twice) and evaluates every function in one qe_window_eval. partition_by: expressions; order_by:
+    twice) and evaluates every function in one qe_window_eval (one qe_window_eval_frames when a
+    function has bounds=(lo, hi) or is FirstValue / LastValue). partition_by: expressions; order_by:
     (Expression, ascending, nulls_first) triples; functions: WindowExpressions. Yields ONE batch in the
     INPUT's row order: the input's columns, then one column per function (`schema` names them). An
     empty input gives a 0-row batch; without keys the whole input is one partition of peers and no
@@ -405,7 +429,7 @@ class WindowExec(PhysicalPlan):
                 slot = next((i for i, c in enumerate(inputs) if c is cv), len(inputs))
                 if slot == len(inputs):
                     inputs.append(cv)
-            fns.append((f.fn, f.frame, slot, f.offset))
+            fns.append((f.fn, f.frame, slot, f.offset) + (f.bounds or (0, 0)))
         for c in part + okeys + inputs:
             if not isinstance(c, DeviceColumn):
                 raise N.IllegalStateException(N.QE_ERR_UNSUPPORTED, "a window key or input must evaluate to a column")
@@ -422,7 +446,11 @@ class WindowExec(PhysicalPlan):
             order = DeviceColumn(N.TYPE_INT32, n, torch.arange(max(n, 1), dtype=torch.int32, device=ctx.torch_device), ctx=ctx)
         part_starts = window_boundaries(part, order)
         peer_starts = window_boundaries(keys, order) if okeys else part_starts
-        yield RecordBatch(schema, list(batch.fields) + window_eval(order, part_starts, peer_starts, inputs, fns))
+        if any(f.frame == N.FRAME_ROWS_BETWEEN or f.fn in (N.WIN_FIRST_VALUE, N.WIN_LAST_VALUE) for f in self.functions):
+            outs = window_eval_frames(order, part_starts, peer_starts, inputs, fns)
+        else:  # a plan without the newer ids runs the call it always ran
+            outs = window_eval(order, part_starts, peer_starts, inputs, [f[:4] for f in fns])
+        yield RecordBatch(schema, list(batch.fields) + outs)
 
     def __repr__(self) -> str:
         return f"WindowExec: partition_by={self.partition_by}, order_by={self.order_by}, functions={self.functions}"
